@@ -7,19 +7,31 @@ per-field threshold (inference.py:72-79) producing bit-packed masks, plus -- for
 the RCCL all-gather of the masks over xGMI into a preallocated buffer.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--global-batch G] [--dtype mixed]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (the driver does this for N>1)
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed steps,
+the output dump when asked for, the JSON line (`value`, `ms_per_step`, `compute_ms`, `allgather_ms`;
+the other legs' fields null or empty).  --full adds every other measurement described below (the
+strong-scaling shapes, the roofline and per-kernel tables, the fp32 / config-5 / batch-1 legs and the
+CPU baseline with its IoU); the --no-* options switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the last timed step left in the gathered mask buffer -- what a caller of
+the step receives -- as DIR/masks.npy: float32 0/1 masks [k, 3, S, S] of a fixed, seeded sample of k
+images of the global batch (all of them when they fit DUMP_BYTES).  Pages and weights are seeded, so two
+builds run with the same arguments can be compared mask for mask.
 
 Launch: under torchrun (WORLD_SIZE set) every process is one rank; WORLD_SIZE must equal --gpus
 (exit 2 otherwise).  Without WORLD_SIZE and --gpus N > 1 the script spawns its own N rank
 processes (127.0.0.1 rendezvous) before any GPU call and exits with the worst rank's code.
 
 Scaling: by default every GPU holds --batch images per step (weak scaling, the headline `value`);
---global-batch G splits G images over the ranks instead (strong scaling).  The same run also
+--global-batch G splits G images over the ranks instead (strong scaling).  A --full run also
 times the strong-scaling shapes of BASELINE's multi-GPU configurations -- global batch 256
 (north_star's "1 -> 8 GPUs at batch 256": 32 images per rank at N = 8) and 1024 (config 4: 128
 per rank) -- as `strong_scaling`.
 
-Rank 0 prints ONE JSON line.  Extra fields: roofline (dominant kernel, HIP-event timed inside
+Rank 0 prints ONE JSON line.  Extra fields (--full): roofline (dominant kernel, HIP-event timed inside
 this run), cpu_baseline (the oracle on this host's cores, bounded sample), fp32 (BASELINE
 config 2: batch 32, 512^2, the drop-in's default precision, against the 157.3 TF fp32 MFMA
 peak), cfg5 (BASELINE config 5 per GPU: 1024^2, fp16, batch 64), latency_bs1 (the drop-in run_unet
@@ -424,6 +436,29 @@ def time_leg(leg, steps, warmup, sync, dev, per_step_events=False):
     return out
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this much float32 (16 of the 256 headline images)
+DUMP_SEED = 20240
+
+
+def sample_masks(rows, budget=DUMP_BYTES):
+    """The gathered bit-packed masks [n, 3, S, S/8] (uint8, any device) as float32 0/1 masks [k, 3, S, S]
+    on the host: all n images when they fit ``budget`` bytes, else a fixed seeded sample of k of them in
+    batch order (the same images for the same n and S); of an image larger than the budget, its leading
+    rows.  Only the sampled rows are copied from the device."""
+    n, f, h, wb = rows.shape
+    per_image = f * h * wb * 8 * 4
+    k = min(n, max(1, budget // per_image))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    keep_h = min(h, max(1, budget // (f * wb * 8 * 4)))
+    packed = rows[torch.from_numpy(idx).to(rows.device)][:, :, :keep_h].cpu().numpy()
+    return np.unpackbits(packed, axis=-1, bitorder="little").astype(np.float32)
+
+
+def dump_outputs(out_dir, masks):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "masks.npy"), masks)
+
+
 def over_ranks(v, dev):
     """(max, min) of a per-rank scalar over the ranks (one all-reduce each; v itself at world 1)."""
     if not dist.is_initialized() or dist.get_world_size() == 1:
@@ -724,6 +759,13 @@ def main():
     ap.add_argument("--channels", type=int, default=3)
     ap.add_argument("--dtype", default="mixed", choices=["mixed", "bf16", "fp16", "fp32", "fp32_exact"])
     ap.add_argument("--weights", default="pretrained", choices=["pretrained", "structured"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: strong-scaling shapes, per-launch "
+                         "profile and roofline, fp32 / config-5 / batch-1 legs, CPU baseline and IoU "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the masks of the last timed step (a fixed seeded sample of the global batch, "
+                         "float32 0/1) to DIR/masks.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
@@ -749,6 +791,8 @@ def main():
                     help="PMC summary (tools/pmc_summary.py output) to fill roofline.traffic; 'auto' = "
                          "profiles/pmc_<dtype>_bs<batch>.json when present (collected by tools/gpu_round.sh)")
     args = ap.parse_args()
+    if args.strong_global and not args.full:
+        ap.error("--strong-global names legs of a --full run")
 
     # ---- launch: one process per GPU.  Self-spawn before any GPU call when not under torchrun.
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -787,7 +831,7 @@ def main():
     strong = args.global_batch is not None
     legs_cfg = [("main", args.global_batch if strong else None, None if strong else args.batch)]
     strong_global = args.strong_global or (STRONG_GLOBAL if S == 512 else ())
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         legs_cfg += [(f"strong_{g}", g, None) for g in strong_global if not (strong and g == args.global_batch)]
     chunk = max(args.batch, udist.shard_bounds(args.global_batch, 0, world)[1]) if strong else args.batch
     runner.reserve(chunk, S)
@@ -802,8 +846,10 @@ def main():
     # per-rank compute (the forwards of its shard, before the exchange): MAX and MIN over the ranks, so a
     # scaling line splits lost efficiency into compute imbalance and exchange
     comp_max, comp_min = over_ranks(float(np.mean(res["compute_ms"])), dev)
+    if args.dump_outputs and rank == 0:   # the last timed step's gathered masks, before any other leg runs
+        dump_outputs(args.dump_outputs, sample_masks(main_leg["gather"].rows()))
 
-    # ---- strong-scaling shapes (same timing protocol, fewer steps)
+    # ---- --full: strong-scaling shapes (same timing protocol, fewer steps)
     strong_out = []
     for name, g, _ in legs_cfg[1:]:
         leg = make_leg(runner, rank, world, g, None, 3000, S, C, dev, chunk, collective)
@@ -814,18 +860,18 @@ def main():
                            "steps": min(args.steps, 10)})
         del leg
 
-    # ---- per-launch HIP-event timing (same stream) -> dominant kernel roofline
+    # ---- --full: per-launch HIP-event timing (same stream) -> dominant kernel roofline
     kernels, roofline, layer_ms, whole = {}, None, {}, None
-    if not args.no_layer_profile and not args.standin and B > 0:
+    if args.full and not args.no_layer_profile and not args.standin and B > 0:
         kernels, layer_ms, roofline, gflop, _ = kernel_table(runner, None, main_leg["x"], main_leg["gather"].local,
                                                              B, S, C, args.dtype, args.traffic_json)
         whole = round(gflop / (res["ms_per_step"]), 1)   # algorithmic TFLOP/s of the timed step
         roofline["whole_step_tflops"] = whole
 
-    # ---- rank 0 at N=1: fp32 config-2 leg, CPU baseline, batch-1 latency
+    # ---- --full, rank 0 at N=1: fp32 config-2 leg, CPU baseline, batch-1 latency
     fp32 = cfg5 = cpu = lat = None
     extra = []
-    solo = rank == 0 and world == 1 and not args.standin
+    solo = args.full and rank == 0 and world == 1 and not args.standin
     if solo and not args.no_fp32 and S == 512 and not args.dtype.startswith("fp32"):
         fp32 = fp32_leg(args, runner, dev)
     if solo and not args.no_cfg5 and S == 512:

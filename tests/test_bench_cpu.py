@@ -61,7 +61,7 @@ def test_strong_legs_chunked_two_ranks():
     """A strong-scaling leg whose shard is larger than the workspace chunk (global 10 over 2 ranks =
     5 images per rank, chunk = --batch 2) runs as 3 chunked forwards + the one all-gather, at
     world 2 -- the path the strong_1024 leg takes on 1 and 2 GPUs."""
-    p, lines = _run([sys.executable, BENCH, "--gpus", "2", "--batch", "2", "--strong-global", "10"] + SMALL)
+    p, lines = _run([sys.executable, BENCH, "--gpus", "2", "--batch", "2", "--full", "--strong-global", "10"] + SMALL)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads(lines[0])
     (leg,) = out["strong_scaling"]
@@ -85,7 +85,7 @@ def test_world_eight_ragged_strong_legs(launcher, tmp_path):
     forwards of --batch images) plus a ragged global batch (1021 = 5 x 128 + 3 x 127): the line reports
     the MAX-over-ranks compute time beside the all-gather's, and the ragged shard sizes."""
     detail = tmp_path / "d.json"
-    args = [BENCH, "--gpus", "8", "--batch", "32", "--strong-global", "256", "1024", "1021",
+    args = [BENCH, "--gpus", "8", "--batch", "32", "--full", "--strong-global", "256", "1024", "1021",
             "--detail-out", str(detail), "--standin", "--size", "16", "--steps", "2", "--warmup", "1"]
     if launcher == "self":
         cmd = [sys.executable] + args
@@ -179,6 +179,62 @@ def test_dist_mode_at_world_one_runs_the_exchange(tmp_path):
     p, lines = _run([sys.executable, BENCH, "--gpus", "1", "--batch", "4", "--detail-out", ""] + SMALL)
     assert p.returncode == 0, p.stderr[-3000:]
     assert json.loads(lines[0])["config"]["exchange"] is None
+
+
+def test_plain_run_has_no_other_legs_and_full_is_asked_for_by_name():
+    """Without --full the line holds the headline and the other legs' fields empty; the options that
+    shape a --full leg are refused rather than ignored."""
+    p, lines = _run([sys.executable, BENCH, "--gpus", "1", "--batch", "4", "--detail-out", ""] + SMALL)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["value"] == pytest.approx(4 / (1e-3 * out["ms_per_step"]), rel=1e-2)
+    assert out["strong_scaling"] == [] and out["roofline"] is None and out["cpu_baseline"] is None
+    assert out["fp32"] is None and out["cfg5"] is None and out["latency_bs1"] is None
+    p, lines = _run([sys.executable, BENCH, "--gpus", "1", "--batch", "4", "--strong-global", "8"] + SMALL)
+    assert p.returncode == 2 and not lines and "--full" in p.stderr
+
+
+def test_dump_outputs_writes_the_last_steps_masks_reproducibly(tmp_path):
+    """--dump-outputs: masks.npy holds the gathered masks of the timed step as float32 0/1 (here the
+    stand-in's function of the seeded pages, over two ranks), identical from run to run."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import bench
+    got = []
+    for d in ("a", "b"):
+        p, lines = _run([sys.executable, BENCH, "--gpus", "2", "--batch", "3", "--detail-out", "",
+                         "--dump-outputs", str(tmp_path / d)] + SMALL)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert os.listdir(tmp_path / d) == ["masks.npy"]
+        got.append(np.load(tmp_path / d / "masks.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (6, 3, 32, 32)
+    assert np.array_equal(got[0], got[1])
+    import torch
+    packed = torch.empty((6, 3, 32, 4), dtype=torch.uint8)
+    segment = bench.StandinRunner(None, torch.device("cpu"), 2).segment_fn()
+    for r in range(2):     # make_leg's shards: rank r forwards gen_pages(1000 + r) into rows [3 r, 3 r + 3)
+        segment(torch.from_numpy(bench.gen_pages(1000 + r, 3, 32, 3)), packed[3 * r:3 * r + 3])
+    assert np.array_equal(got[0], np.unpackbits(packed.numpy(), axis=-1, bitorder="little").astype(np.float32))
+    assert 0 < got[0].mean() < 1
+
+
+def test_dump_sample_is_fixed_and_within_its_budget():
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    rows = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (40, 3, 16, 2), dtype=np.uint8))
+    per_image = 3 * 16 * 16 * 4
+    a = bench.sample_masks(rows, budget=7 * per_image + 5)
+    assert a.shape == (7, 3, 16, 16) and a.dtype == np.float32 and a.nbytes <= 7 * per_image + 5
+    assert np.array_equal(a, bench.sample_masks(rows.clone(), budget=7 * per_image + 5))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(40, size=7, replace=False))
+    assert np.array_equal(a, np.unpackbits(rows.numpy()[idx], axis=-1, bitorder="little"))
+    assert bench.sample_masks(rows, budget=40 * per_image).shape == (40, 3, 16, 16)      # everything fits
+    assert bench.sample_masks(rows, budget=per_image // 2).shape == (1, 3, 8, 16)        # leading rows of one image
+    # the headline shape (256 images at 512^2) stays under 64 MB
+    assert 0 < (bench.DUMP_BYTES // (3 * 512 * 512 * 4)) * 3 * 512 * 512 * 4 <= bench.DUMP_BYTES <= 64 << 20
 
 
 def test_summary_line_is_compact():

@@ -307,7 +307,7 @@ def test_bench_dist_world_one_line(tmp_path):
     detail = tmp_path / "detail.json"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--dist", "--batch", "8",
-                        "--size", "256", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-latency",
+                        "--size", "256", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-latency",
                         "--no-fp32", "--no-cfg5", "--no-strong", "--detail-out", str(detail)],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=170)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -17,5 +17,6 @@ if [ "$MODE" != "skip-tests" ]; then
 fi
 [ "$MODE" = "tests-only" ] && exit 0
 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --detail-out gpurun_out/bench_$TAG.detail.json \
+    --full \
     > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
 echo bench ok

@@ -22,7 +22,7 @@ if [ "$MODE" != "skip-tests" ] && [ "$MODE" != "bench-only" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1
   echo smoke ok
 fi
-P="--no-cpu-baseline --no-latency --no-strong --no-fp32 --no-cfg5"
+P="--full --no-cpu-baseline --no-latency --no-strong --no-fp32 --no-cfg5"   # the per-launch profile only
 PASSES=("FETCH_SIZE" "WRITE_SIZE"
         "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE")
 profile() {   # profile SUFFIX TRAFFIC_JSON BENCH_ARGS...
@@ -56,6 +56,7 @@ echo fp32 profiles ok
 fi
 [ "$MODE" = "no-bench" ] && exit 0
 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --detail-out gpurun_out/bench_$TAG.detail.json \
+    --full \
     > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
 echo bench ok
 # the profiles of this pass against the bench line of the same box (tools/stamp_profiles.py)
@@ -64,6 +65,6 @@ if [ "$MODE" != "bench-only" ]; then
       --pmc gpurun_out/pmc_$TAG/summary.json --bench gpurun_out/bench_$TAG.json --out gpurun_out/stamp_$TAG.json \
       > /dev/null && echo stamp ok
 fi
-timeout -k 10 300 python bench.py --size 1024 --batch 64 --dtype fp16 --steps 5 --warmup 3 --cpu-seconds 10 --no-latency \
+timeout -k 10 300 python bench.py --full --size 1024 --batch 64 --dtype fp16 --steps 5 --warmup 3 --cpu-seconds 10 --no-latency \
     --no-strong --detail-out gpurun_out/bench_${TAG}_cfg5.detail.json > gpurun_out/bench_${TAG}_cfg5_fp16_1024.json 2> gpurun_out/bench_${TAG}_cfg5.err
 echo bench cfg5 ok
