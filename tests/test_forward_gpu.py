@@ -281,6 +281,118 @@ def test_nan_input_propagates_like_torch(dtype):
     m.close()
 
 
+FLOOR = 1e-4   # folded weights of _positive_state_dict are raised towards this; asserted: normal fp16 numbers
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+def _positive_state_dict(seed, probe):
+    """Structured weights made to carry an infinity through to the logits: |w| on every 3x3 conv and
+    ConvTranspose, and every BatchNorm re-calibrated on ``probe`` (running statistics = the layer's own
+    pre-BN statistics, gamma 1, beta 0.5) so that activations stay O(1) although all weights are positive.
+    inf * w is then +inf in every layer and never meets a -inf.  out_conv: class 0 all positive (+inf),
+    class 1 all negative (-inf), class 2 alternating signs (NaN).  Every folded weight is raised
+    to a normal fp16 number (>= 2^-14, aiming at 1e-4), so that none rounds to zero in fp16 storage:
+    a zero weight would make inf * 0 = NaN of it (without the floor sixteen folded weights of down2 and conv2
+    fall below fp16's smallest subnormal, and the mixed plan then has NaN where the oracle has +-inf)."""
+    import torch.nn.functional as F
+    sd = {k: np.array(v) for k, v in syn.make_state_dict(seed, 3, 3, profile="structured").items()}
+    for k, v in sd.items():
+        if k.endswith("weight") and v.ndim == 4:
+            sd[k] = np.maximum(np.abs(v) / (16.0 if k.startswith("up") else 1.0), FLOOR if k.startswith("up") else 0.0)
+    sd["out_conv.weight"][1] *= -1
+    sd["out_conv.weight"][2, ::2] *= -1
+    t = lambda k: torch.from_numpy(sd[k])   # noqa: E731
+
+    def dc(name, v):
+        for conv, bn in ((0, 1), (3, 4)):
+            wk = f"{name}.net.{conv}.weight"
+            for _ in range(6):   # raising weights raises the variance, which lowers the fold's scale: iterate
+                y = F.conv2d(v, t(wk), t(f"{name}.net.{conv}.bias"), padding=1)
+                scale = 1.0 / np.sqrt(y.var((0, 2, 3)).numpy() + 1e-3)           # the fold's scale, gamma = 1
+                if (sd[wk] * scale.reshape(-1, 1, 1, 1)).min() >= 1.2 * FLOOR:
+                    break
+                sd[wk] = np.maximum(sd[wk], (2 * FLOOR / scale).astype(np.float32).reshape(-1, 1, 1, 1))
+            y = F.conv2d(v, t(wk), t(f"{name}.net.{conv}.bias"), padding=1)
+            sd[f"{name}.net.{bn}.running_mean"] = y.mean((0, 2, 3)).numpy()
+            sd[f"{name}.net.{bn}.running_var"] = (y.var((0, 2, 3)) + 1e-3).numpy()
+            sd[f"{name}.net.{bn}.weight"] = np.ones(y.shape[1], np.float32)
+            sd[f"{name}.net.{bn}.bias"] = np.full(y.shape[1], 0.5, np.float32)
+            v = F.relu(F.batch_norm(y, t(f"{name}.net.{bn}.running_mean"), t(f"{name}.net.{bn}.running_var"),
+                                    t(f"{name}.net.{bn}.weight"), t(f"{name}.net.{bn}.bias"), training=False, eps=1e-5))
+            folded = sd[wk] / np.sqrt(sd[f"{name}.net.{bn}.running_var"].astype(np.float64) + 1e-5).reshape(-1, 1, 1, 1)
+            assert folded.min() >= F16_MIN_NORMAL, (wk, folded.min())
+        return v
+
+    with torch.no_grad():
+        skips, v = [], torch.from_numpy(probe)
+        for name in ("down1", "down2", "down3", "down4"):
+            skips.append(dc(name, v))
+            v = F.max_pool2d(skips[-1], 2)
+        v = dc("bottleneck", v)
+        for k in (4, 3, 2, 1):
+            v = dc(f"conv{k}", torch.cat([orc.up(sd, f"up{k}", v), skips[k - 1]], 1))
+    return sd
+
+
+_INF_CASES = {}
+
+
+def _inf_case(weights):
+    """(state_dict, input with one +inf and one -inf pixel, oracle logits), computed once per weight set."""
+    if weights not in _INF_CASES:
+        x = syn.uniform_batch(8, 1, 3, 320, 320)
+        sd = syn.make_state_dict(3, 3, 3, profile="structured") if weights == "structured" else \
+            _positive_state_dict(3, np.ascontiguousarray(x[:, :, :64, 64:192]))
+        x[0, 1, 7, 9] = np.inf
+        x[0, 0, 300, 170] = -np.inf
+        _INF_CASES[weights] = (sd, x, orc.unet_forward(sd, torch.from_numpy(x)).numpy())
+    return _INF_CASES[weights]
+
+
+@pytest.mark.parametrize("dtype", ["fp32_exact", "mixed", "fp32"])
+@pytest.mark.parametrize("weights", ["structured", "positive"])
+def test_inf_input_pixels(weights, dtype):
+    """One +inf and one -inf input pixel.  The exact-fp32 plan and the 16-bit plans multiply the infinity by
+    the weight itself, as the reference does: the logits are +inf, -inf or NaN exactly where the oracle's are,
+    a +inf logit gives a True mask (sigmoid(+inf) = 1), NaN and -inf a False one.  The three-term fp32 plan
+    cannot keep the kind: it evaluates inf * w as inf * w_hi + inf * w_mid + inf * w_lo, which is inf - inf
+    when w_mid has the other sign and inf * 0 when w is a bf16 value, so every logit the infinity reaches is
+    NaN -- the SET of non-finite logits is the oracle's, the finite ones are within tolerance,
+    and a non-finite logit gives a False mask.
+
+    "structured": dense weights of both signs; the oracle's own infinities meet as inf - inf in the second
+    conv already, so its non-finite logits are all NaN.  "positive" (_positive_state_dict): the +inf pixel
+    reaches the logits as +inf in class 0, -inf in class 1 and NaN in class 2 (asserted), and the -inf pixel
+    ends at the first ReLU, as in the reference.  There the finite logits are held to the tolerance in the
+    fp32 plans only: the re-calibrated BatchNorm subtracts a mean many times the spread, which multiplies a
+    16-bit storage error by that ratio, and the 16-bit tolerances were set on zero-mean weights."""
+    sd, x, ref = _inf_case(weights)
+    m = make_model(sd, 3, dtype)
+    with torch.no_grad():
+        masks, lg = m.forward_masks(torch.from_numpy(x).to(DEV), with_logits=True)
+    lg, masks = lg.cpu().numpy(), masks.cpu().numpy().astype(bool)
+    bad_ref, bad_got = ~np.isfinite(ref), ~np.isfinite(lg)
+    err = rel_err(lg[~bad_ref & ~bad_got], ref[~bad_ref & ~bad_got])
+    print(f"{weights} {dtype}: non-finite logits {int(bad_got.sum())} (oracle {int(bad_ref.sum())}: "
+          f"{int(np.isnan(ref).sum())} NaN, {int(np.isposinf(ref).sum())} +inf, {int(np.isneginf(ref).sum())} -inf) "
+          f"of {lg.size}; finite logits rel err {err:.3e}")
+    assert 0 < bad_ref.sum() < ref.size
+    if weights == "positive":
+        assert np.isposinf(ref[0, 0]).sum() > 1000 and np.isneginf(ref[0, 1]).sum() > 1000 and np.isnan(ref[0, 2]).sum() > 1000
+        assert np.isfinite(ref[0, :, 300, 170]).all()        # the -inf pixel: relu(-inf) = 0
+    assert np.array_equal(bad_got, bad_ref)
+    if weights == "structured" or dtype != "mixed":
+        assert err <= TOL[dtype]
+    if dtype == "fp32":
+        assert not masks[bad_got].any()
+    else:
+        assert np.array_equal(np.isnan(lg), np.isnan(ref))
+        assert np.array_equal(np.isposinf(lg), np.isposinf(ref))
+        assert np.array_equal(np.isneginf(lg), np.isneginf(ref))
+        assert masks[np.isposinf(lg)].all() and not masks[np.isnan(lg) | np.isneginf(lg)].any()
+    m.close()
+
+
 def test_logit_cut_matches_torch_sigmoid_on_gpu():
     """The fused masks threshold logits at the host-bisected cut (unet_logit_cut); the reference
     thresholds torch.sigmoid.  Against ROCm's own sigmoid on the GPU, every fp32 logit within

@@ -966,9 +966,11 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   h->cfg = *cfg;
   const bool f32 = cfg->dtype == UNET_DTYPE_F32 || cfg->dtype == UNET_DTYPE_F32_EXACT;
   // the three-term plan: 2 = the split-once 128-row tiles on the Cout >= 128 layers (x3 = 3), 64-row tiles
-  // splitting per tap elsewhere (x3 = 2); 1 = x3 = 2 everywhere; 0 = exact fp32 (UNET_MI355X_F32X3: A/B runs)
+  // splitting per tap elsewhere (x3 = 2); 1 = x3 = 2 everywhere; 0 = exact fp32 (UNET_MI355X_F32X3: A/B runs
+  // of the "fp32" plan only -- "fp32_exact" stays on the exact-fp32 MFMA whatever the variable says)
   h->f32x3 = cfg->dtype == UNET_DTYPE_F32 ? 2 : 0;
-  if (const char* x3 = std::getenv("UNET_MI355X_F32X3")) h->f32x3 = f32 ? std::atoi(x3) : 0;
+  if (const char* x3 = std::getenv("UNET_MI355X_F32X3"))
+    if (cfg->dtype == UNET_DTYPE_F32) h->f32x3 = std::atoi(x3);
   h->dt = f32 ? DType::F32 : DType::BF16;   // workspace element size (all 16-bit plans: 2 bytes)
   for (int i = 0; i < kMaxClasses; ++i) h->thr_logit[i] = unet_logit_cut(cfg->thresholds[i]);
   // Kernel configuration per layer (tuned on MI355X).  A/B override for tuning:
@@ -1854,7 +1856,8 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out) {
   h.cfg.device = cfg->device;
   h.ksplit_max = 0;
   h.f32x3 = cfg->dtype == UNET_DTYPE_F32;
-  if (const char* x3 = std::getenv("UNET_MI355X_F32X3")) h.f32x3 = f32 && std::atoi(x3) != 0;   // A/B runs
+  if (const char* x3 = std::getenv("UNET_MI355X_F32X3"))   // A/B runs of the "fp32" plan only
+    if (cfg->dtype == UNET_DTYPE_F32) h.f32x3 = std::atoi(x3) != 0;
   // the mixed plan's storage type at this block's resolution level in the reference network: fp16 up to
   // 128 channels (levels 0-1), bf16 beyond (levels 2-4)
   const DType t = f32 ? DType::F32 : cfg->dtype == UNET_DTYPE_F16 ? DType::F16 : cfg->dtype == UNET_DTYPE_BF16 ? DType::BF16

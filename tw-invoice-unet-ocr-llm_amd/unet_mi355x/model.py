@@ -160,11 +160,20 @@ class DoubleConv(_Tracked, nn.Module):
 class UNet(_Tracked, nn.Module):
     """unet_model.UNet(n_channels=3, n_classes=3) with an MI355X forward.
 
-    compute_dtype: "fp32" (default; exact fp32 MFMA, reference semantics), "bf16" or
+    compute_dtype: "fp32" (default; fp32 storage, every product as three bf16 terms per operand
+    on the bf16 MFMA with fp32 accumulation -- fp32 accuracy, not bitwise fp32 products),
+    "fp32_exact" (fp32 storage with true fp32 products on the fp32 MFMA, reference semantics), "bf16" or
     "fp16" (16-bit activations/weights, fp32 accumulation, fp32 head), or "mixed" (bf16 at
     resolution levels 2-4, fp16 at the full-resolution levels 0-1; the benchmark's plan, chosen
     so the masks meet IoU >= 0.999 against fp32).  Default from the UNET_MI355X_DTYPE
     environment variable.
+
+    Non-finite input pixels: NaN propagates as through the reference in every plan.  +-inf does so
+    by kind and sign in "fp32_exact" and the 16-bit plans (a +inf logit gives a True mask; a weight
+    that rounds to zero in the 16-bit type makes inf * 0 = NaN of it).  The
+    three-term "fp32" plan evaluates inf * w as inf * w_hi + inf * w_mid + inf * w_lo, which is
+    inf - inf or inf * 0, so there every logit an infinity reaches is NaN: the set of non-finite
+    logits is the reference's, each of them gives a False mask.
 
     Inference only: the native forward folds eval-mode BatchNorm and builds no autograd graph, so
     calling it in training mode with grad enabled raises (use the reference module to train).
