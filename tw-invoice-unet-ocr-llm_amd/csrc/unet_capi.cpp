@@ -180,10 +180,56 @@ const int kLayerCh[17][2] = {{64, 64},    {64, 128},   {128, 128}, {128, 256}, {
                              {256, 512},  {512, 512},  {512, 1024}, {1024, 1024},
                              {1024, 512}, {512, 512},  {512, 256}, {256, 256},
                              {256, 128},  {128, 128},  {128, 64},  {64, 64}};
-// Resolution level (0 = full resolution) of each 3x3 layer's input and output; EPI_POOL layers
-// also write a pooled map one level down.  ConvTranspose up_k reads level k and writes k-1.
-const int kLayerLevel[17] = {0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0};
-const int kUpLevel[4] = {4, 3, 2, 1};   // input level of up4..up1
+const char* kUpKey[4] = {"up4", "up3", "up2", "up1"};
+const int kUpCh[4][2] = {{1024, 512}, {512, 256}, {256, 128}, {128, 64}};
+
+// The launch sequence of UNet.forward (unet_model.py:55-86), slots 1..21 of UNET_NUM_LAUNCHES (slot 0 is the first
+// conv or the input pre-cast): the one table forward_impl, build_labels_at, split_bytes, unet_debug_fetch and
+// unet_create's layer set-up walk.  resolve() applies what depends on the handle.
+//   id     0..16 = L[], 17 + j = ConvTranspose j (up4..up1)
+//   level  resolution level (0 = full resolution) of a 3x3 layer's input and output; EPI_POOL layers also write a
+//          pooled map one level down (out2).  ConvTranspose up_k reads level k and writes k-1.
+//   name   unet_debug_fetch's name of `out` (nc channels at out_off), pname that of the pooled map
+// encoder: conv b of each level writes the skip into the upper half of the concat buffer (torch.cat([up, skip])
+// puts skip second, unet_model.py:71) and the pooled map; decoder: up_k writes the lower half of the concat
+// buffer, conv_k reads all of it; conv1.net.3 + BN + ReLU + out_conv (1x1) + sigmoid/threshold is one launch.
+struct Launch {
+  int id, epi, level;
+  size_t Buffers::*in;
+  int ldi;
+  size_t Buffers::*out;
+  int ldo, out_off;
+  size_t Buffers::*out2;
+  int ldo2;
+  const char* name;
+  int nc;
+  const char* pname;
+};
+#define B_(m) &Buffers::m
+const Launch kLaunches[] = {
+    {D1B, EPI_POOL, 0, B_(tA), 64, B_(cat1), 128, 64, B_(p1), 64, "c1", 64, "p1"},
+    {D2A, EPI_STORE, 1, B_(p1), 64, B_(tA), 128},
+    {D2B, EPI_POOL, 1, B_(tA), 128, B_(cat2), 256, 128, B_(p2), 128, "c2", 128, "p2"},
+    {D3A, EPI_STORE, 2, B_(p2), 128, B_(tA), 256},
+    {D3B, EPI_POOL, 2, B_(tA), 256, B_(cat3), 512, 256, B_(p3), 256, "c3", 256, "p3"},
+    {D4A, EPI_STORE, 3, B_(p3), 256, B_(tA), 512},
+    {D4B, EPI_POOL, 3, B_(tA), 512, B_(cat4), 1024, 512, B_(p4), 512, "c4", 512, "p4"},
+    {BNA, EPI_STORE, 4, B_(p4), 512, B_(tA), 1024},
+    {BNB, EPI_STORE, 4, B_(tA), 1024, B_(bnb), 1024, 0, {}, 0, "bn", 1024},
+    {17, EPI_UPSCATTER, 4, B_(bnb), 1024, B_(cat4), 1024, 0, {}, 0, "u4", 512},
+    {C4A, EPI_STORE, 3, B_(cat4), 1024, B_(tA), 512},
+    {C4B, EPI_STORE, 3, B_(tA), 512, B_(tB), 512},
+    {18, EPI_UPSCATTER, 3, B_(tB), 512, B_(cat3), 512, 0, {}, 0, "u3", 256},
+    {C3A, EPI_STORE, 2, B_(cat3), 512, B_(tA), 256},
+    {C3B, EPI_STORE, 2, B_(tA), 256, B_(tB), 256},
+    {19, EPI_UPSCATTER, 2, B_(tB), 256, B_(cat2), 256, 0, {}, 0, "u2", 128},
+    {C2A, EPI_STORE, 1, B_(cat2), 256, B_(tA), 128},
+    {C2B, EPI_STORE, 1, B_(tA), 128, B_(tB), 128, 0, {}, 0, "c7", 128},
+    {20, EPI_UPSCATTER, 1, B_(tB), 128, B_(cat1), 128, 0, {}, 0, "u1", 64},
+    {C1A, EPI_STORE, 0, B_(cat1), 128, B_(tA), 64, 0, {}, 0, "c8a", 64},
+    {C1B, EPI_HEAD, 0, B_(tA), 64}};
+#undef B_
+static_assert(sizeof kLaunches / sizeof kLaunches[0] == UNET_NUM_LAUNCHES - 1, "one row per launch slot after the first");
 // Default kernel configuration per 3x3 layer, from in-process A/B timing on MI355X at bs256
 // 512x512 (tools/tune.py; profiles/tune_r1*.txt).
 //   16-bit: the 64-byte-row ring kernel; 128-row wave tiles on every layer with Cout >= 128
@@ -208,8 +254,6 @@ const int kHaloCfg[17] = {
     CFG_HALO_R128, CFG_HALO_R128, CFG_HALO_R128, CFG_HALO_R128, CFG_HALO_R128, CFG_HALO_R128,
     CFG_HALO_R128, CFG_HALO_R128,                       // down2.0 .. conv2.3
     CFG_HALO_R64_W4, CFG_HALO_R64_W8};                  // conv1.0, conv1.3 (+head)
-const char* kUpKey[4] = {"up4", "up3", "up2", "up1"};
-const int kUpCh[4][2] = {{1024, 512}, {512, 256}, {256, 128}, {128, 64}};
 
 // Storage precision of a level under the handle's dtype.  UNET_DTYPE_MIXED: fp16 at the two
 // full-resolution levels 0-1 (where the mask boundaries are decided), bf16 at levels 2-4.
@@ -248,9 +292,10 @@ struct Split {
   int ks = 1;     // K slices (1 = the layer runs unsplit)
   int rows = 0;   // 8-wave ring: row tile of the slices (64 = halves of the 128-row packing), 0 = the layer's own
 };
+// id: the launch's split-plan id (Launch::id, the index of UNET_MI355X_KSPLIT_FORCE); < 0 = never split
 Split layer_split(const unet_handle* h, int id, const Layer& L, int epi, int N, int Hl, int Wl) {
   Split best;
-  if (h->ksplit_max <= 1 || N <= 0 || N > kSmallBatch || Hl <= 0 || Wl <= 0) return best;
+  if (id < 0 || h->ksplit_max <= 1 || N <= 0 || N > kSmallBatch || Hl <= 0 || Wl <= 0) return best;
   const bool ring8 = L.cfg == CFG_RING8_R128 && L.dt != DType::F32 && L.taps == 9;
   const bool halo = cfg_is_halo(L.cfg) && L.dt == DType::F32;
   if (L.cfg == CFG_TRING_R256 && L.dt != DType::F32 && epi == EPI_UPSCATTER) {
@@ -317,24 +362,44 @@ Split layer_split(const unet_handle* h, int id, const Layer& L, int epi, int N, 
   return best;
 }
 
-// Launch order of forward_impl with each launch's layer, epilogue and input level, for the split-K
-// plan's workspace bound (the largest partial buffer of one launch).
+// A row of kLaunches as this handle runs it at batch N -- the only place that knows the variations:
+//   fuse_up1: conv2.3 becomes EPI_UPFUSE writing up1's half of cat1 through out2 (its own output, "c7", is not
+//     stored) and up1's slot launches nothing (L == nullptr);
+//   the fused first conv: down1.3 is never split (r.id < 0; run_igemm hands its kernel x0, w0r and b0);
+//   the small-batch ConvTranspose variant (up_layer).
+struct Step {
+  Launch r;         // r.id: layer_split's id
+  const Layer* L;   // nullptr: the slot launches nothing
+};
+Step resolve(const unet_handle* h, const Launch& row, int N) {
+  Step st{row, nullptr};
+  if (row.id >= 17) {
+    if (!(row.id == 20 && h->fuse_up1)) st.L = &up_layer(h, row.id - 17, N);
+    return st;
+  }
+  st.L = &h->L[row.id];
+  if (row.id == C2B && h->fuse_up1) {
+    st.r.epi = EPI_UPFUSE;
+    st.r.out = nullptr;
+    st.r.ldo = 0;
+    st.r.out2 = &Buffers::cat1;
+    st.r.ldo2 = 128;
+  }
+  if (row.id == D1B && cfg_fused_in(st.L->cfg)) st.r.id = -1;
+  return st;
+}
+Split step_split(const unet_handle* h, const Step& st, int N, int H, int W) {
+  return layer_split(h, st.r.id, *st.L, st.r.epi, N, H >> st.r.level, W >> st.r.level);
+}
+
+// The split-K plan's workspace bound: the largest partial buffer of one launch.
 size_t split_bytes(const unet_handle* h, int N, int H, int W) {
   size_t m = 0;
-  auto one = [&](int id, const Layer& L, int epi, int lvl) {
-    const int Hl = H >> lvl, Wl = W >> lvl;
-    const int ks = layer_split(h, id, L, epi, N, Hl, Wl).ks;
-    if (ks > 1) m = std::max(m, (size_t)ks * N * Hl * Wl * L.ctot * 4);
-  };
-  for (int i = 0; i < 17; ++i) {
-    const bool pool = i == D1B || i == D2B || i == D3B || i == D4B;
-    int epi = pool ? EPI_POOL : i == C1B ? EPI_HEAD : EPI_STORE;
-    if (i == C2B && h->fuse_up1) epi = EPI_UPFUSE;
-    if (i == D1B && cfg_fused_in(h->L[D1B].cfg)) continue;
-    one(i, h->L[i], epi, kLayerLevel[i]);
+  for (const Launch& row : kLaunches) {
+    const Step st = resolve(h, row, N);
+    const int ks = st.L ? step_split(h, st, N, H, W).ks : 1;
+    if (ks > 1) m = std::max(m, (size_t)ks * N * (H >> row.level) * (W >> row.level) * st.L->ctot * 4);
   }
-  for (int j = 0; j < 4; ++j)
-    if (!(j == 3 && h->fuse_up1)) one(17 + j, up_layer(h, j, N), EPI_UPSCATTER, kUpLevel[j]);
   return m;
 }
 
@@ -686,6 +751,54 @@ int ensure_box_sync(unet_handle* h, int n) {
   return UNET_OK;
 }
 
+// The plumbing unet_* and unet_block_* share.  A new handle's completion event and zero page (the caller has set
+// the device and deletes the handle on failure):
+int init_handle(unet_handle* h) {
+  hipError_t e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
+  if (e != hipSuccess) return fail(UNET_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+  std::vector<uint8_t> z(4096, 0);   // zero page: conv padding source, + 64 B per K chunk (ring halo cursors)
+  const int rc = upload(h, &h->zero, z.data(), z.size());
+  if (rc) { free_all(h); (void)hipEventDestroy(h->done); }
+  return rc;
+}
+// before a weight load: everything but the zero page goes
+void reset_weights(unet_handle* h) {
+  drain(h);   // in-flight forwards may still read the weights about to be freed
+  ++h->generation;
+  for (void* p : h->allocs)
+    if (p != h->zero) (void)hipFree(p);
+  h->allocs.assign(1, h->zero);
+  h->loaded = false;
+}
+// a workspace of at least `need` bytes
+int grow_workspace(unet_handle* h, size_t need, const char* what) {
+  if (need <= h->ws_bytes) return UNET_OK;
+  DeviceGuard g(h->cfg.device);
+  ++h->generation;
+  if (h->ws) {
+    drain(h);   // the old workspace may still be in use by queued forwards
+    (void)hipFree(h->ws);
+    h->ws = nullptr;
+    h->ws_bytes = 0;
+  }
+  hipError_t e = hipMalloc((void**)&h->ws, need);
+  if (e != hipSuccess) {
+    h->ws = nullptr;
+    return fail(UNET_ENOMEM, std::string(what) + " hipMalloc: " + hipGetErrorString(e));
+  }
+  h->ws_bytes = need;
+  return UNET_OK;
+}
+// The three-term fp32 plan (unet_handle::f32x3) of a dtype: 2 = the split-once 128-row tiles on the Cout >= 128
+// layers (x3 = 3), 64-row tiles splitting per tap elsewhere (x3 = 2); 1 = x3 = 2 everywhere; 0 = exact fp32
+// (UNET_MI355X_F32X3: A/B runs of the "fp32" plan only -- "fp32_exact" stays on the exact-fp32 MFMA whatever the
+// variable says)
+int f32x3_plan(int dtype) {
+  if (dtype != UNET_DTYPE_F32) return 0;
+  const char* x3 = std::getenv("UNET_MI355X_F32X3");
+  return x3 ? std::atoi(x3) : 2;
+}
+
 // ---- Pillow's resize coefficients (libImaging/Resample.c: precompute_coeffs +
 // normalize_coeffs_8bpc, BICUBIC a = -0.5, support 2), same double-precision operation order
 #pragma clang fp contract(off)
@@ -786,15 +899,14 @@ const char* tname(DType t) { return t == DType::F32 ? "float" : t == DType::BF16
 // "kernel<template args>" of a layer, in the same spelling as the demangled symbol.  sp: the
 // small-batch plan's choice for the launch (layer_split): a split layer runs its EPI_PARTIAL kernel and
 // the reduction ("A + B"), finer row tiles the 64-row 8-wave ring / the 128-row ConvTranspose ring.
-std::string layer_label(const unet_handle* h, const Layer& L, int epi, Split sp = Split{}) {
+std::string layer_label(const Layer& L, int epi, Split sp = Split{}) {
   char buf[160];
   int cfg = L.cfg;
-  (void)h;
   if (sp.ks == 1 && sp.rows && cfg == CFG_TRING_R256) cfg = CFG_TRING_R128;   // run_igemm's batch-1 halves
   if (sp.ks > 1) {   // launch_igemm(..., EPI_PARTIAL) + launch_splitk_reduce
     Layer P = L;
     P.dto = P.dtq = L.dt;
-    std::string part = layer_label(h, P, EPI_PARTIAL, Split{1, sp.rows});
+    std::string part = layer_label(P, EPI_PARTIAL, Split{1, sp.rows});
     std::snprintf(buf, sizeof buf, " + splitk_reduce_kernel<%s, %s, %d>", tname(L.dto),
                   tname(epi == EPI_POOL ? L.dtq : L.dto), epi);
     return part + buf;
@@ -831,48 +943,36 @@ void build_labels_at(const unet_handle* h, int N, int H, int W, std::string (&ou
   const DType t0 = h->L[D1B].dt;
   std::snprintf(buf, sizeof buf, t0 == DType::F32 ? "first_conv_kernel<%s, %d>" : "first_conv_mfma_kernel<%s, %d>",
                 tname(t0), C);
-  // launch order (include/unet_mi355x.h): first, d1b .. bnb, up4, c4a, c4b, up3, c3a, c3b, up2, c2a, c2b, up1, c1a, c1b
-  const int order[UNET_NUM_LAUNCHES] = {-1, D1B, D2A, D2B, D3A, D3B, D4A, D4B, BNA, BNB, 100, C4A, C4B,
-                                        101, C3A, C3B, 102, C2A, C2B, 103, C1A, C1B};
-  for (int i = 0; i < UNET_NUM_LAUNCHES; ++i) {
-    const int id = order[i];
-    if (id < 0) {
-      out[i] = cfg_fused_in(h->L[D1B].cfg) ? std::string("x_to_px4_kernel<") + tname(t0) + ">" : buf;
-      continue;
-    }
-    if (id >= 100) {   // a fused up1 launches nothing: empty label (tools: its time and work go to conv2.3)
-      const int j = id - 100;
-      out[i] = (j == 3 && h->fuse_up1) ? std::string()
-                                       : layer_label(h, up_layer(h, j, N), EPI_UPSCATTER,
-                                                     layer_split(h, 17 + j, up_layer(h, j, N), EPI_UPSCATTER, N,
-                                                                 H >> kUpLevel[j], W >> kUpLevel[j]));
-      continue;
-    }
-    int epi = id == C1B ? EPI_HEAD : (id == D1B || id == D2B || id == D3B || id == D4B) ? EPI_POOL : EPI_STORE;
-    if (id == C2B && h->fuse_up1) epi = EPI_UPFUSE;
-    out[i] = layer_label(h, h->L[id], epi,
-                         layer_split(h, id, h->L[id], epi, N, H >> kLayerLevel[id], W >> kLayerLevel[id]));
+  // launch order (include/unet_mi355x.h): first, then kLaunches
+  out[0] = cfg_fused_in(h->L[D1B].cfg) ? std::string("x_to_px4_kernel<") + tname(t0) + ">" : buf;
+  int i = 1;
+  for (const Launch& row : kLaunches) {
+    const Step st = resolve(h, row, N);
+    // a fused up1 launches nothing: empty label (tools: its time and work go to conv2.3)
+    out[i++] = st.L ? layer_label(*st.L, st.r.epi, step_split(h, st, N, H, W)) : std::string();
   }
 }
 void build_labels(unet_handle* h) { build_labels_at(h, 0, 0, 0, h->labels); }
 
-// "layer:cfg,..." override list (tools/tune.py A/B runs)
-void parse_overrides(const char* ov, int n, int* cfg_out, bool (*ok)(int, int)) {
-  if (!ov) return;
-  std::string o(ov);
-  size_t pos = 0;
-  while (pos < o.size()) {
-    size_t end = o.find(',', pos);
-    if (end == std::string::npos) end = o.size();
+// The "i:v,..." lists of the A/B override variables: each(i, v, item) for every item with a colon; the caller
+// decides what it accepts.
+template <typename F>
+void parse_pairs(const char* list, F each) {
+  const std::string o(list ? list : "");
+  for (size_t pos = 0, end; pos < o.size(); pos = end + 1) {
+    end = std::min(o.find(',', pos), o.size());
     const std::string item = o.substr(pos, end - pos);
     const size_t colon = item.find(':');
-    if (colon != std::string::npos) {
-      const int li = std::atoi(item.substr(0, colon).c_str()), c = std::atoi(item.substr(colon + 1).c_str());
-      if (li >= 0 && li < n && c >= 0 && c < cfg_limit() && ok(li, c)) cfg_out[li] = c;
-      else std::fprintf(stderr, "unet_mi355x: ignoring configuration override '%s'\n", item.c_str());
-    }
-    pos = end + 1;
+    if (colon != std::string::npos)
+      each(std::atoi(item.substr(0, colon).c_str()), std::atoi(item.substr(colon + 1).c_str()), item);
   }
+}
+// "layer:cfg,..." override list (tools/tune.py A/B runs)
+void parse_overrides(const char* ov, int n, int* cfg_out, bool (*ok)(int)) {
+  parse_pairs(ov, [&](int li, int c, const std::string& item) {
+    if (li >= 0 && li < n && c >= 0 && c < cfg_limit() && ok(c)) cfg_out[li] = c;
+    else std::fprintf(stderr, "unet_mi355x: ignoring configuration override '%s'\n", item.c_str());
+  });
 }
 
 // RCCL, resolved at run time (dlopen) so the library has no link-time dependency on it and a
@@ -965,12 +1065,7 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   unet_handle* h = new unet_handle();
   h->cfg = *cfg;
   const bool f32 = cfg->dtype == UNET_DTYPE_F32 || cfg->dtype == UNET_DTYPE_F32_EXACT;
-  // the three-term plan: 2 = the split-once 128-row tiles on the Cout >= 128 layers (x3 = 3), 64-row tiles
-  // splitting per tap elsewhere (x3 = 2); 1 = x3 = 2 everywhere; 0 = exact fp32 (UNET_MI355X_F32X3: A/B runs
-  // of the "fp32" plan only -- "fp32_exact" stays on the exact-fp32 MFMA whatever the variable says)
-  h->f32x3 = cfg->dtype == UNET_DTYPE_F32 ? 2 : 0;
-  if (const char* x3 = std::getenv("UNET_MI355X_F32X3"))
-    if (cfg->dtype == UNET_DTYPE_F32) h->f32x3 = std::atoi(x3);
+  h->f32x3 = f32x3_plan(cfg->dtype);
   h->dt = f32 ? DType::F32 : DType::BF16;   // workspace element size (all 16-bit plans: 2 bytes)
   for (int i = 0; i < kMaxClasses; ++i) h->thr_logit[i] = unet_logit_cut(cfg->thresholds[i]);
   // Kernel configuration per layer (tuned on MI355X).  A/B override for tuning:
@@ -981,15 +1076,18 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   // tile whose two weight slots of three bf16 planes leave two blocks per CU)
   for (int i = 0; i < 17; ++i) cfgs[i] = h->f32x3 ? (int)CFG_HALO_R64_W4 : f32 ? kHaloCfg[i] : kRingCfg[i];
   for (int i = 0; i < 4; ++i) ucfgs[i] = f32 ? (int)CFG_HALO_R128 : (int)CFG_TRING_R256;
-  parse_overrides(std::getenv("UNET_MI355X_CFG"), 17, cfgs, [](int, int c) { return cfg_is_halo(c) || cfg_is_ring(c); });
-  parse_overrides(std::getenv("UNET_MI355X_UPCFG"), 4, ucfgs, [](int, int c) { return cfg_is_tring(c) || c == CFG_HALO_R128; });
-  for (int i = 0; i < 17; ++i) {
+  parse_overrides(std::getenv("UNET_MI355X_CFG"), 17, cfgs, [](int c) { return cfg_is_halo(c) || cfg_is_ring(c); });
+  parse_overrides(std::getenv("UNET_MI355X_UPCFG"), 4, ucfgs, [](int c) { return cfg_is_tring(c) || c == CFG_HALO_R128; });
+  for (const Launch& row : kLaunches) {
+    if (row.id >= 17) continue;
+    const int i = row.id;
+    const bool pool = row.epi == EPI_POOL;
     Layer& L = h->L[i];
     L.cin = kLayerCh[i][0];
     L.cout = L.ctot = kLayerCh[i][1];
     L.taps = 9;
-    L.dt = L.dto = level_dtype(cfg->dtype, kLayerLevel[i]);
-    L.dtq = level_dtype(cfg->dtype, kLayerLevel[i] + 1);
+    L.dt = L.dto = level_dtype(cfg->dtype, row.level);
+    L.dtq = level_dtype(cfg->dtype, row.level + 1);
     int c = cfgs[i];
     // keep every layer on a configuration it supports, within the same kernel family (the
     // configurations of a family accumulate in the same K order, so they agree bitwise)
@@ -1003,7 +1101,6 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
     if (cfg_rows(c) > L.cout || (i == C1B && cfg_rows(c) != 64))
       c = ring ? CFG_RING_R64_T3 : CFG_HALO_R64_W8;
     // the LDS-halo family stores its own operand type only: keep it off the mixed plan's seams
-    const bool pool = i == D1B || i == D2B || i == D3B || i == D4B;
     if (cfg_is_halo(c) && (L.dto != L.dt || (pool && L.dtq != L.dt))) c = L.cout == 64 || pool ? CFG_RING_R64_T3 : CFG_RING_R128;
     if (c == CFG_RING_R128 && pool) c = CFG_RING_R64_T3;   // pooled 128-row 4-wave tiles spill: same family, 64 rows
     if (h->f32x3 && f32) {   // the three-term plan: pre-split weights; split-once tiles (f32x3 = 2) of 128 rows
@@ -1020,14 +1117,16 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
     }
     L.cfg = c;
   }
-  for (int i = 0; i < 4; ++i) {
+  for (const Launch& row : kLaunches) {
+    if (row.id < 17) continue;
+    const int i = row.id - 17;
     Layer& U = h->U[i];
     U.cin = kUpCh[i][0];
     U.cout = kUpCh[i][1];
     U.ctot = 4 * kUpCh[i][1];
     U.taps = 1;
-    U.dt = level_dtype(cfg->dtype, kUpLevel[i]);
-    U.dto = U.dtq = level_dtype(cfg->dtype, kUpLevel[i] - 1);
+    U.dt = level_dtype(cfg->dtype, row.level);
+    U.dto = U.dtq = level_dtype(cfg->dtype, row.level - 1);
     U.cfg = (ucfgs[i] == CFG_HALO_R128 && U.dto != U.dt) ? (int)CFG_TRING_R256 : ucfgs[i];
     if (h->f32x3 && f32) {   // both operands split on the fly on 128-row tiles
       U.cfg = CFG_HALO_R128;
@@ -1046,26 +1145,13 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
                   u1.dt == c2b.dt && u1.dto == c2b.dto;
   }
   if (const char* ks = std::getenv("UNET_MI355X_KSPLIT")) h->ksplit_max = std::atoi(ks);
-  if (const char* kf = std::getenv("UNET_MI355X_KSPLIT_FORCE")) {   // "i:ks,..." (A/B runs)
-    std::string o(kf);
-    size_t pos = 0;
-    while (pos < o.size()) {
-      size_t end = o.find(',', pos);
-      if (end == std::string::npos) end = o.size();
-      const std::string item = o.substr(pos, end - pos);
-      const size_t colon = item.find(':');
-      const int li = colon == std::string::npos ? -1 : std::atoi(item.substr(0, colon).c_str());
-      if (li >= 0 && li < 21) h->ksplit_force[li] = std::atoi(item.substr(colon + 1).c_str());
-      pos = end + 1;
-    }
-  }
+  parse_pairs(std::getenv("UNET_MI355X_KSPLIT_FORCE"), [&](int li, int ks, const std::string&) {   // "i:ks,..." (A/B runs)
+    if (li >= 0 && li < 21) h->ksplit_force[li] = ks;
+  });
   build_labels(h);   // after every layer's configuration (3x3 and ConvTranspose) is final
   DeviceGuard g(cfg->device);
-  hipError_t e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
-  if (e != hipSuccess) { delete h; return fail(UNET_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-  std::vector<uint8_t> z(4096, 0);   // zero page: conv padding source, + 64 B per K chunk (ring halo cursors)
-  int rc = upload(h, &h->zero, z.data(), z.size());
-  if (rc) { free_all(h); (void)hipEventDestroy(h->done); delete h; return rc; }
+  const int rc = init_handle(h);
+  if (rc) { delete h; return rc; }
   *out = h;
   return UNET_OK;
 }
@@ -1083,12 +1169,7 @@ int unet_load_weights(unet_handle* h, const unet_tensor_view* t, int n) {
     return fail(UNET_EKEY, "state_dict has " + std::to_string(sd.m.size()) + " keys, expected " +
                                std::to_string(expected));
   DeviceGuard g(h->cfg.device);
-  drain(h);   // in-flight forwards may still read the weights about to be freed
-  ++h->generation;
-  for (void* p : h->allocs)
-    if (p != h->zero) (void)hipFree(p);
-  h->allocs.assign(1, h->zero);
-  h->loaded = false;
+  reset_weights(h);
 
   std::vector<double> w, b;
   const int C = h->cfg.n_channels;
@@ -1204,27 +1285,13 @@ int unet_reserve(unet_handle* h, int N, int H, int W) {
   const size_t need = plan(h, N, H, W).total;
   DeviceGuard g(h->cfg.device);
   rc = ensure_box_sync(h, N * h->cfg.n_classes);
-  if (rc) return rc;
-  if (need <= h->ws_bytes) return UNET_OK;
-  ++h->generation;
-  if (h->ws) {
-    drain(h);   // the old workspace may still be in use by queued forwards
-    (void)hipFree(h->ws);
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-  }
-  hipError_t e = hipMalloc((void**)&h->ws, need);
-  if (e != hipSuccess) {
-    h->ws = nullptr;
-    return fail(UNET_ENOMEM, std::string("workspace hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->ws_bytes = need;
-  return UNET_OK;
+  return rc ? rc : grow_workspace(h, need, "workspace");
 }
 
 namespace {
 
-int run_igemm(unet_handle* h, const Layer& L, int epi, const void* in, int N, int H, int W, int ldi,
+// id: layer_split's (Step::r.id; < 0 = never split: the fused first conv, the stand-alone block)
+int run_igemm(unet_handle* h, int id, const Layer& L, int epi, const void* in, int N, int H, int W, int ldi,
               void* out, int ldo, int out_off, void* out2, int ldo2, hipStream_t s,
               float* logits = nullptr, void* masks = nullptr, int mask_kind = MASK_NONE,
               const void* x0 = nullptr) {
@@ -1260,8 +1327,6 @@ int run_igemm(unet_handle* h, const Layer& L, int epi, const void* in, int N, in
   a.tiles_x = (W + cfg_tile_w(L.cfg) - 1) / cfg_tile_w(L.cfg);
   a.tiles_y = (H + cfg_tile_h(L.cfg) - 1) / cfg_tile_h(L.cfg);
   a.n_ct = L.ctot / cfg_rows(L.cfg);
-  const int id = (&L >= h->L && &L < h->L + 17) ? (int)(&L - h->L)
-                 : (&L >= h->Us && &L < h->Us + 4) ? 17 + (int)(&L - h->Us) : 17 + (int)(&L - h->U);
   const Split sp = layer_split(h, id, L, epi, N, H, W);
   int cfg = L.cfg;
   if (sp.ks == 1 && sp.rows) {   // small-batch plan, unsplit: finer row tiles over the layer's packing
@@ -1316,7 +1381,6 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
     masks = buf(B.mbits);
     mask_kind = UNET_MASK_BITS;
   }
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16;
   const int C = h->cfg.n_channels;
 
   int li = 0;
@@ -1349,40 +1413,18 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
     if (e != hipSuccess) return fail(UNET_EHIP, std::string("first conv launch: ") + hipGetErrorString(e));
   }
 
-#define RUN(...) do { mark(); rc = run_igemm(__VA_ARGS__); if (rc) return rc; } while (0)
-  // encoder: conv b of each level writes the skip into the upper half of the concat
-  // buffer (torch.cat([up, skip]) puts skip second, unet_model.py:71) and the pooled map.
-  RUN(h, h->L[D1B], EPI_POOL, buf(B.tA), N, H, W, 64, buf(B.cat1), 128, 64, buf(B.p1), 64, s,
-      nullptr, nullptr, MASK_NONE, x0);
-  RUN(h, h->L[D2A], EPI_STORE, buf(B.p1), N, H2, W2, 64, buf(B.tA), 128, 0, nullptr, 0, s);
-  RUN(h, h->L[D2B], EPI_POOL, buf(B.tA), N, H2, W2, 128, buf(B.cat2), 256, 128, buf(B.p2), 128, s);
-  RUN(h, h->L[D3A], EPI_STORE, buf(B.p2), N, H4, W4, 128, buf(B.tA), 256, 0, nullptr, 0, s);
-  RUN(h, h->L[D3B], EPI_POOL, buf(B.tA), N, H4, W4, 256, buf(B.cat3), 512, 256, buf(B.p3), 256, s);
-  RUN(h, h->L[D4A], EPI_STORE, buf(B.p3), N, H8, W8, 256, buf(B.tA), 512, 0, nullptr, 0, s);
-  RUN(h, h->L[D4B], EPI_POOL, buf(B.tA), N, H8, W8, 512, buf(B.cat4), 1024, 512, buf(B.p4), 512, s);
-  RUN(h, h->L[BNA], EPI_STORE, buf(B.p4), N, H16, W16, 512, buf(B.tA), 1024, 0, nullptr, 0, s);
-  RUN(h, h->L[BNB], EPI_STORE, buf(B.tA), N, H16, W16, 1024, buf(B.bnb), 1024, 0, nullptr, 0, s);
-  // decoder: up_k writes the lower half of the concat buffer, conv_k reads all of it
-  RUN(h, up_layer(h, 0, N), EPI_UPSCATTER, buf(B.bnb), N, H16, W16, 1024, buf(B.cat4), 1024, 0, nullptr, 0, s);
-  RUN(h, h->L[C4A], EPI_STORE, buf(B.cat4), N, H8, W8, 1024, buf(B.tA), 512, 0, nullptr, 0, s);
-  RUN(h, h->L[C4B], EPI_STORE, buf(B.tA), N, H8, W8, 512, buf(B.tB), 512, 0, nullptr, 0, s);
-  RUN(h, up_layer(h, 1, N), EPI_UPSCATTER, buf(B.tB), N, H8, W8, 512, buf(B.cat3), 512, 0, nullptr, 0, s);
-  RUN(h, h->L[C3A], EPI_STORE, buf(B.cat3), N, H4, W4, 512, buf(B.tA), 256, 0, nullptr, 0, s);
-  RUN(h, h->L[C3B], EPI_STORE, buf(B.tA), N, H4, W4, 256, buf(B.tB), 256, 0, nullptr, 0, s);
-  RUN(h, up_layer(h, 2, N), EPI_UPSCATTER, buf(B.tB), N, H4, W4, 256, buf(B.cat2), 256, 0, nullptr, 0, s);
-  RUN(h, h->L[C2A], EPI_STORE, buf(B.cat2), N, H2, W2, 256, buf(B.tA), 128, 0, nullptr, 0, s);
-  if (h->fuse_up1) {   // conv2.3 + up1 in one launch (EPI_UPFUSE): up1's slot launches nothing
-    RUN(h, h->L[C2B], EPI_UPFUSE, buf(B.tA), N, H2, W2, 128, nullptr, 0, 0, buf(B.cat1), 128, s);
-    mark();
-  } else {
-    RUN(h, h->L[C2B], EPI_STORE, buf(B.tA), N, H2, W2, 128, buf(B.tB), 128, 0, nullptr, 0, s);
-    RUN(h, up_layer(h, 3, N), EPI_UPSCATTER, buf(B.tB), N, H2, W2, 128, buf(B.cat1), 128, 0, nullptr, 0, s);
+  auto at = [&](size_t Buffers::*m) { return m ? buf(B.*m) : nullptr; };
+  for (const Launch& row : kLaunches) {
+    mark();   // every slot, the fused up1's (which launches nothing) included: unet_forward_timed's numbering
+    const Step st = resolve(h, row, N);
+    if (!st.L) continue;
+    const Launch& r = st.r;
+    const bool head = r.epi == EPI_HEAD;   // the only launch that writes the logits and masks
+    rc = run_igemm(h, r.id, *st.L, r.epi, at(r.in), N, H >> r.level, W >> r.level, r.ldi, at(r.out), r.ldo,
+                   r.out_off, at(r.out2), r.ldo2, s, head ? static_cast<float*>(logits) : nullptr,
+                   head ? masks : nullptr, head ? mask_kind : (int)MASK_NONE, x0);
+    if (rc) return rc;
   }
-  RUN(h, h->L[C1A], EPI_STORE, buf(B.cat1), N, H, W, 128, buf(B.tA), 64, 0, nullptr, 0, s);
-  // conv1.net.3 + BN + ReLU + out_conv (1x1) + sigmoid/threshold, one launch
-  RUN(h, h->L[C1B], EPI_HEAD, buf(B.tA), N, H, W, 64, nullptr, 0, 0, nullptr, 0, s,
-      static_cast<float*>(logits), masks, mask_kind);
-#undef RUN
   if (boxes) {   // per-(image, field) mask bounding boxes (inference.py:84-90)
     hipError_t e = launch_mask_boxes(static_cast<const uint8_t*>(masks), mask_kind, N, h->cfg.n_classes, H, W,
                                      boxes, h->box_sync, s);
@@ -1507,21 +1549,20 @@ int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel
   if (!h->lastN) return fail(UNET_ESTATE, "no forward has run");
   const int N = h->lastN, H = h->lastH, W = h->lastW;
   const Buffers B = plan(h, N, H, W);
-  struct Src { size_t off; int level, C, ld, choff; };
-  static const std::map<std::string, int> idx = {
-      {"c1", 0}, {"p1", 1}, {"c2", 2}, {"p2", 3}, {"c3", 4}, {"p3", 5}, {"c4", 6}, {"p4", 7},
-      {"bn", 8}, {"c7", 9}, {"u1", 10}, {"u2", 11}, {"u3", 12}, {"u4", 13}, {"c8a", 14}};
-  auto it = idx.find(name);
-  if (it == idx.end()) return fail(UNET_EINVAL, std::string("unknown intermediate ") + name);
-  if (it->second == 9 && h->last_fused)
+  // the launch whose output (or pooled map) carries the name, as the table's rows place it
+  const Launch* r = nullptr;
+  bool pooled = false;
+  for (const Launch& row : kLaunches) {
+    const bool p = row.pname && !std::strcmp(row.pname, name);
+    if (p || (row.name && !std::strcmp(row.name, name))) { r = &row; pooled = p; }
+  }
+  if (!r) return fail(UNET_EINVAL, std::string("unknown intermediate ") + name);
+  if (r->id == C2B && h->last_fused)
     return fail(UNET_ESTATE, "c7 (conv2.3's output) is not stored when up1 is fused into conv2.3 "
                              "(set UNET_MI355X_FUSE_UP1=0 before creating the handle to keep it)");
-  const Src table[] = {{B.cat1, 0, 64, 128, 64},   {B.p1, 1, 64, 64, 0},     {B.cat2, 1, 128, 256, 128},
-                       {B.p2, 2, 128, 128, 0},     {B.cat3, 2, 256, 512, 256}, {B.p3, 3, 256, 256, 0},
-                       {B.cat4, 3, 512, 1024, 512}, {B.p4, 4, 512, 512, 0},  {B.bnb, 4, 1024, 1024, 0},
-                       {B.tB, 1, 128, 128, 0},     {B.cat1, 0, 64, 128, 0},  {B.cat2, 1, 128, 256, 0},
-                       {B.cat3, 2, 256, 512, 0},   {B.cat4, 3, 512, 1024, 0}, {B.tA, 0, 64, 64, 0}};
-  const Src& t = table[it->second];
+  struct Src { size_t off; int level, C, ld, choff; };
+  const Src t = pooled ? Src{B.*r->out2, r->level + 1, r->nc, r->ldo2, 0}
+                       : Src{B.*r->out, r->id >= 17 ? r->level - 1 : r->level, r->nc, r->ldo, r->out_off};
   const int h_ = H >> t.level, w_ = W >> t.level;
   const size_t cnt = (size_t)N * t.C * h_ * w_;
   if (numel) *numel = cnt;
@@ -1551,8 +1592,7 @@ int unet_graph_create(unet_handle* h, const void* x, int x_layout, int x_dtype, 
     rc = fail(UNET_EHIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
   } else {
     h->capturing = true;
-    rc = boxes ? forward_impl(h, x, x_layout, x_dtype, logits, masks, mask_kind, boxes, N, H, W, cs, nullptr)
-               : forward_impl(h, x, x_layout, x_dtype, logits, masks, mask_kind, nullptr, N, H, W, cs, nullptr);
+    rc = forward_impl(h, x, x_layout, x_dtype, logits, masks, mask_kind, boxes, N, H, W, cs, nullptr);
     h->capturing = false;
     e = hipStreamEndCapture(cs, &gr->graph);
     if (!rc && e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1855,9 +1895,7 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out) {
   h.cfg.dtype = cfg->dtype;
   h.cfg.device = cfg->device;
   h.ksplit_max = 0;
-  h.f32x3 = cfg->dtype == UNET_DTYPE_F32;
-  if (const char* x3 = std::getenv("UNET_MI355X_F32X3"))   // A/B runs of the "fp32" plan only
-    if (cfg->dtype == UNET_DTYPE_F32) h.f32x3 = std::atoi(x3) != 0;
+  h.f32x3 = f32x3_plan(cfg->dtype) != 0;
   // the mixed plan's storage type at this block's resolution level in the reference network: fp16 up to
   // 128 channels (levels 0-1), bf16 beyond (levels 2-4)
   const DType t = f32 ? DType::F32 : cfg->dtype == UNET_DTYPE_F16 ? DType::F16 : cfg->dtype == UNET_DTYPE_BF16 ? DType::BF16
@@ -1876,11 +1914,8 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out) {
     else L.cfg = cout == 64 ? (L.cin == 64 ? CFG_RING8_R64_WS : CFG_RING8_R64_T9) : CFG_RING8_R128;
   }
   DeviceGuard g(cfg->device);
-  hipError_t e = hipEventCreateWithFlags(&h.done, hipEventDisableTiming);
-  if (e != hipSuccess) { delete b; return fail(UNET_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-  std::vector<uint8_t> z(4096, 0);
-  int rc = upload(&h, &h.zero, z.data(), z.size());
-  if (rc) { free_all(&h); (void)hipEventDestroy(h.done); delete b; return rc; }
+  const int rc = init_handle(&h);
+  if (rc) { delete b; return rc; }
   *out = b;
   return UNET_OK;
 }
@@ -1898,12 +1933,7 @@ int unet_block_load_weights(unet_block* b, const unet_tensor_view* t, int n) {
     return fail(UNET_EKEY, "DoubleConv state_dict has " + std::to_string(sd.m.size()) + " keys, expected 14");
   unet_handle& h = b->core;
   DeviceGuard g(h.cfg.device);
-  drain(&h);
-  ++h.generation;
-  for (void* p : h.allocs)
-    if (p != h.zero) (void)hipFree(p);
-  h.allocs.assign(1, h.zero);
-  h.loaded = false;
+  reset_weights(&h);
   std::vector<double> w, bb;
   int rc = fold(sd, "b", "0", b->cin, b->cout, w, bb);
   if (!rc) rc = check_f16_range(h.L[0].dt, w, bb, "net.0");
@@ -1934,24 +1964,7 @@ int unet_block_reserve(unet_block* b, int N, int H, int W) {
   if (!b) return fail(UNET_EINVAL, "null block");
   int rc = block_geometry(N, H, W);
   if (rc) return rc;
-  unet_handle& h = b->core;
-  const size_t need = block_plan(b, N, H, W).total;
-  if (need <= h.ws_bytes) return UNET_OK;
-  DeviceGuard g(h.cfg.device);
-  ++h.generation;
-  if (h.ws) {
-    drain(&h);
-    (void)hipFree(h.ws);
-    h.ws = nullptr;
-    h.ws_bytes = 0;
-  }
-  hipError_t e = hipMalloc((void**)&h.ws, need);
-  if (e != hipSuccess) {
-    h.ws = nullptr;
-    return fail(UNET_ENOMEM, std::string("block workspace hipMalloc: ") + hipGetErrorString(e));
-  }
-  h.ws_bytes = need;
-  return UNET_OK;
+  return grow_workspace(&b->core, block_plan(b, N, H, W).total, "block workspace");
 }
 
 int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, int W, void* stream) {
@@ -1982,10 +1995,10 @@ int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, in
   } else {
     e = launch_nchw_to_nhwc(t, x, N, b->cin, H, W, h.ws + B.in, s);
     if (e != hipSuccess) return fail(UNET_EHIP, std::string("block input transpose: ") + hipGetErrorString(e));
-    rc = run_igemm(&h, h.L[0], EPI_STORE, h.ws + B.in, N, H, W, b->cin, mid, b->cout, 0, nullptr, 0, s);
+    rc = run_igemm(&h, -1, h.L[0], EPI_STORE, h.ws + B.in, N, H, W, b->cin, mid, b->cout, 0, nullptr, 0, s);
     if (rc) return rc;
   }
-  rc = run_igemm(&h, h.L[1], EPI_STORE, mid, N, H, W, b->cout, outb, b->cout, 0, nullptr, 0, s);
+  rc = run_igemm(&h, -1, h.L[1], EPI_STORE, mid, N, H, W, b->cout, outb, b->cout, 0, nullptr, 0, s);
   if (rc) return rc;
   e = launch_nhwc_to_nchw(t, outb, N, b->cout, H, W, y, s);
   if (e != hipSuccess) return fail(UNET_EHIP, std::string("block output transpose: ") + hipGetErrorString(e));
