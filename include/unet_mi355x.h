@@ -15,7 +15,8 @@
  *   - device pointers are caller-owned (e.g. torch data_ptr()); work is enqueued on the
  *     caller's HIP stream (hipStream_t passed as void*), with no hidden synchronisation
  *     except inside unet_load_weights / unet_reserve (allocation + upload) and the first
- *     unet_preprocess of a new photo geometry (coefficient upload).  unet_forward never
+ *     unet_preprocess of a new photo geometry (coefficient upload), and unet_score_reserve or a
+ *     unet_score whose scratch is too small (allocation).  unet_forward never
  *     allocates: size the workspace with unet_reserve first.
  *   - a handle owns one workspace.  Calls on it must not overlap on the host (serialise them;
  *     the Python wrapper holds a lock).  On the device, a call issued on a different stream than
@@ -35,7 +36,9 @@ extern "C" {
 #define UNET_ABI_VERSION 5   /* 2: unet_forward requires unet_reserve; Cfg renumbered; fp16 range check. 3: unet_crop_stats.
                                  4: unet_launch_label_at, unet_small_batch_limit, unet_photo_graph_create, unet_block_*
                                  5: unet_photo_graph_set_masks (the masks copy is its own node); UNET_DTYPE_F32 as
-                                    three bf16 terms, UNET_DTYPE_F32_EXACT the exact-fp32 MFMA */
+                                    three bf16 terms, UNET_DTYPE_F32_EXACT the exact-fp32 MFMA
+                                    (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
+                                    UNET_TGT_*) */
 
 /* error codes */
 #define UNET_OK 0
@@ -255,6 +258,46 @@ int unet_comm_get_unique_id(void* id);
 int unet_comm_init(unet_handle* h, int rank, int nranks, const void* id);
 int unet_allgather(unet_handle* h, const void* send, void* recv, size_t bytes_per_rank, void* hip_stream);
 int unet_comm_destroy(unet_handle* h);
+
+/* Scoring of labelled pages on the device: what train.py:129-160 keeps a checkpoint by (InvoiceLoss,
+ * train.py:18-59), the per-field mask IoU, and a threshold sweep -- 64 bytes per (image, field) come back instead
+ * of the logits.
+ * target forms: */
+#define UNET_TGT_F32_NCHW 0  /* fp32 [N][C][H][W], values in [0,1]: the tensor dataset.py:33-34 hands the loss */
+#define UNET_TGT_U8_NHWC 1   /* uint8 [N][H][W][C], v read as v / 255.0f: the .npy mask files of dataset.py:32 */
+/* Per element, in fp32 and op by op as the reference (train.py:58, 24-29, 40-45; gamma = 2, alpha is the host's):
+ *   p = 1 / (1 + expf(-x));  pt = p * t;  pc = clamp(p, 1e-7f, (float)(1 - 1e-7));
+ *   bce = (t - 1) * max(logf(1 - pc), -100) - t * max(logf(pc), -100);  q = expf(-bce);  u = 1 - q;  f = u * u * bce
+ * accumulated per (n, c) in fp64 over a summation tree that depends on H * W only: an entry is bitwise reproducible
+ * and independent of N and of the other images of the batch.  n_pred counts x > unet_logit_cut(thr[c]) (the masks
+ * epilogue's predicate), n_tgt counts t > 0.5f (train.py:76), n_both both.  A NaN logit makes the four sums of its
+ * entry NaN and counts as not predicted.  From the entries:
+ *   Dice loss  = mean over (n, c) of 1 - (2 sum_pt + smooth) / (sum_p + sum_t + smooth)
+ *   focal loss = alpha * sum of sum_focal / sum of n_px
+ *   IoU        = n_both / (n_pred + n_tgt - n_both) */
+typedef struct unet_score_entry {
+  double sum_p, sum_t, sum_pt, sum_focal;
+  int64_t n_pred, n_tgt, n_both, n_px;
+} unet_score_entry;
+
+/* Size the handle's score scratch (its own allocation: unet_workspace_bytes / unet_reserve are unaffected) for
+ * scores of up to N images of H x W with up to 4 classes and K sweep candidates (0 = no sweep).  Allocating
+ * waits for the handle's queued work. */
+int unet_score_reserve(unet_handle* h, int N, int H, int W, int K);
+
+/* Score logits (device fp32 NCHW [N][C][H][W], e.g. unet_forward's output; C in 1..4, any H, W >= 1) against
+ * target (device, layout per target_kind).  thresholds: C host floats, NULL = the handle's.  entries: device
+ * unet_score_entry [N][C].
+ * Sweep (optional): sweep_probs = K <= 64 strictly ascending host probabilities and hist = device int64
+ * [N][C][2][K+1]; every element increments hist[n][c][t > 0.5f][b], b = #{k : x > unet_logit_cut(sweep_probs[k])},
+ * so suffix sums over b give n_pred, n_both and n_tgt at every candidate.  Both NULL (K ignored) = no sweep.
+ * Two launches on hip_stream, stream-ordered after the handle's previous call like unet_forward; needs no
+ * weights.  A scratch too small for the call is grown synchronously (like unet_preprocess's first call of a
+ * geometry), except on a stream under capture, where that is UNET_ESTATE: call unet_score_reserve first (a later
+ * growth re-allocates the scratch a captured score reads).  Bad arguments are UNET_EINVAL before any HIP call. */
+int unet_score(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
+               const float* thresholds, unet_score_entry* entries, const float* sweep_probs, int K, int64_t* hist,
+               void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

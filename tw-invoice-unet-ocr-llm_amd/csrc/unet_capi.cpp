@@ -5,6 +5,7 @@
 // the implicit-GEMM kernels, the activation workspace, and the per-forward launch sequence that
 // mirrors UNet.forward (unet_model.py:55-86).
 #include "unet_internal.h"
+#include "unet_score.h"
 #include "../../include/unet_mi355x.h"
 
 #include <dlfcn.h>
@@ -149,6 +150,10 @@ struct unet_handle {
   // launches), grown by unet_reserve
   int* box_sync = nullptr;
   int box_sync_n = 0;
+  // unet_score's partial slabs: its own allocation (the forward workspace and its size are untouched), grown by
+  // unet_score_reserve / unet_score
+  void* score = nullptr;
+  size_t score_bytes = 0;
 };
 
 struct unet_graph {
@@ -723,6 +728,9 @@ void free_all(unet_handle* h) {
   if (h->box_sync) (void)hipFree(h->box_sync);
   h->box_sync = nullptr;
   h->box_sync_n = 0;
+  if (h->score) (void)hipFree(h->score);
+  h->score = nullptr;
+  h->score_bytes = 0;
 }
 
 // At least n idle mask-box sync entries (at least 1024: N * n_classes up to 1024 never reallocates).
@@ -1507,6 +1515,79 @@ int unet_crop_stats(const void* img, int ih, int iw, int channels, const int32_t
                                    pad, rects, reinterpret_cast<unsigned long long*>(sums), nullptr,
                                    static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(UNET_EHIP, std::string("crop stats launch: ") + hipGetErrorString(e));
+  return UNET_OK;
+}
+
+namespace {
+int score_geometry(int N, int H, int W, int K) {
+  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
+  if (K < 0 || K > kScoreMaxK) return fail(UNET_EINVAL, "K (sweep candidates) must be 0..64");
+  if ((long long)N * kMaxClasses * score_spans((long long)H * W) > 0x7FFFFFFFLL)
+    return fail(UNET_EINVAL, "N x H x W too large for one score");
+  return UNET_OK;
+}
+// a score scratch of at least `need` bytes
+int grow_score(unet_handle* h, size_t need) {
+  if (need <= h->score_bytes) return UNET_OK;
+  if (h->score) {
+    drain(h);   // queued scores may still read the old slabs
+    (void)hipFree(h->score);
+    h->score = nullptr;
+    h->score_bytes = 0;
+  }
+  hipError_t e = hipMalloc(&h->score, need);
+  if (e != hipSuccess) {
+    h->score = nullptr;
+    return fail(UNET_ENOMEM, std::string("score scratch hipMalloc: ") + hipGetErrorString(e));
+  }
+  h->score_bytes = need;
+  return UNET_OK;
+}
+}  // namespace
+
+int unet_score_reserve(unet_handle* h, int N, int H, int W, int K) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  const int rc = score_geometry(N, H, W, K);
+  if (rc) return rc;
+  DeviceGuard g(h->cfg.device);
+  return grow_score(h, score_scratch_bytes((long long)N * kMaxClasses, (long long)H * W, K));
+}
+
+int unet_score(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
+               const float* thresholds, unet_score_entry* entries, const float* sweep_probs, int K, int64_t* hist,
+               void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!logits || !target || !entries) return fail(UNET_EINVAL, "logits, target and entries must not be NULL");
+  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
+  if (target_kind != UNET_TGT_F32_NCHW && target_kind != UNET_TGT_U8_NHWC)
+    return fail(UNET_EINVAL, "target_kind must be UNET_TGT_F32_NCHW or UNET_TGT_U8_NHWC");
+  if (hist && !sweep_probs) return fail(UNET_EINVAL, "hist given without sweep_probs");
+  if (sweep_probs && !hist) return fail(UNET_EINVAL, "sweep_probs given without hist");
+  if (!sweep_probs) K = 0;
+  int rc = score_geometry(N, H, W, K);
+  if (rc) return rc;
+  if (sweep_probs && K < 1) return fail(UNET_EINVAL, "K must be 1..64 with sweep_probs");
+  for (int k = 0; k < K; ++k)
+    if (!(sweep_probs[k] > (k ? sweep_probs[k - 1] : -INFINITY)))   // also refuses NaN
+      return fail(UNET_EINVAL, "sweep_probs must be strictly ascending");
+  ScoreCuts cuts{};
+  for (int c = 0; c < C; ++c) cuts.thr[c] = thresholds ? unet_logit_cut(thresholds[c]) : h->thr_logit[c];
+  cuts.K = K;
+  for (int k = 0; k < K; ++k) cuts.sweep[k] = unet_logit_cut(sweep_probs[k]);
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t need = score_scratch_bytes((long long)N * C, (long long)H * W, K);
+  if (need > h->score_bytes) {
+    if (stream_capturing(h, s))
+      return fail(UNET_ESTATE, "score scratch too small on a capturing stream: call unet_score_reserve first");
+    rc = grow_score(h, need);
+    if (rc) return rc;
+  }
+  order_after_last(h, s);
+  hipError_t e = launch_score(logits, target, target_kind, N, C, H, W, cuts, h->score, entries, hist, s);
+  if (e != hipSuccess) return fail(UNET_EHIP, std::string("score launch: ") + hipGetErrorString(e));
+  mark_done(h, s);
   return UNET_OK;
 }
 

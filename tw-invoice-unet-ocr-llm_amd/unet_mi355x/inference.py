@@ -519,3 +519,65 @@ def run_unet_batch(pil_imgs, checkpoint_path: str, compute_dtype: str | None = N
     finish(*pending)
     del keep
     return out
+
+
+def labelled_pages(img_dir: str, mask_dir: str):
+    """The reference dataset's pairs (dataset.py:11-15, 24-26, 32), in sorted order: for every ``.jpg`` /
+    ``.png`` file of ``img_dir`` its stem, the image path (``<stem>.jpg`` if present, else ``<stem>.png``) and
+    ``mask_dir/<stem>.npy``."""
+    out = []
+    for stem in sorted(f.rsplit(".", 1)[0] for f in os.listdir(img_dir) if f.lower().endswith((".jpg", ".png"))):
+        jpg = os.path.join(img_dir, stem + ".jpg")
+        out.append((stem, jpg if os.path.exists(jpg) else os.path.join(img_dir, stem + ".png"),
+                    os.path.join(mask_dir, stem + ".npy")))
+    return out
+
+
+def evaluate(img_dir: str, mask_dir: str, checkpoint_path: str, batch: int = 4, sweep=None,
+             compute_dtype: str | None = None):
+    """Score a checkpoint on a directory of labelled pages: what the reference's training loop keeps a
+    checkpoint by (train.py:129-160), without the logits leaving the GPU.
+
+    The directory is walked as the reference dataset does (``labelled_pages``); a page is its pixels / 255 as
+    fp32 (dataset.py:28-29) at its own size -- all pages one size, H and W divisible by 16 --, its mask the
+    uint8 HWC ``.npy`` file uploaded as stored.  Pages are scored in chunks of ``batch``; the returned
+    ``metrics.Score`` covers all of them in order, so ``.loss(batch=batch)`` is the epoch average train.py
+    prints for an unshuffled loader, ``.iou()`` the per-page mask IoU at the model's thresholds and, with
+    ``sweep`` (ascending probabilities), ``.best_thresholds()`` the per-field choice.
+
+    Images are decoded with Pillow; the reference decodes with cv2, whose JPEG decoder may differ from Pillow's
+    in the last bit of a pixel (PNG is lossless: identical).  Decoder parity for JPEG is not claimed."""
+    from .metrics import Score
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    if not str(DEVICE).startswith("cuda"):
+        raise RuntimeError("unet_mi355x: evaluate runs on a ROCm GPU; there is no CPU fallback")
+    pages = labelled_pages(img_dir, mask_dir)
+    if not pages:
+        raise ValueError(f"no .jpg / .png pages in {img_dir}")
+    model = _cached_model(checkpoint_path, compute_dtype)
+    size = None
+    scores = []
+    for lo in range(0, len(pages), batch):
+        xs, ms = [], []
+        for stem, img_path, mask_path in pages[lo:lo + batch]:
+            with Image.open(img_path) as im:
+                a = np.asarray(im.convert("RGB"))
+            m = np.load(mask_path)
+            if size is None:
+                size = a.shape[:2]
+                if size[0] % 16 or size[1] % 16:
+                    raise ValueError(f"evaluate: page {stem} is {size[1]}x{size[0]}; H and W must be divisible by 16")
+            if a.shape[:2] != size:
+                raise ValueError(f"evaluate: page {stem} is {a.shape[1]}x{a.shape[0]}, the first page "
+                                 f"{size[1]}x{size[0]}; all pages must have one size")
+            if m.dtype != np.uint8 or m.shape != size + (len(FIELDS),):
+                raise ValueError(f"evaluate: mask {mask_path} must be uint8 {size + (len(FIELDS),)}, "
+                                 f"got {m.dtype} {m.shape}")
+            xs.append(a.transpose(2, 0, 1).astype(np.float32) / 255.0)
+            ms.append(m)
+        x = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(DEVICE)
+        t = torch.from_numpy(np.ascontiguousarray(np.stack(ms))).to(DEVICE)
+        with torch.no_grad():
+            scores.append(model.score(x, t, sweep))
+    return Score.concat(scores)

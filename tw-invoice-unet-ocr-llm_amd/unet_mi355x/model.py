@@ -176,7 +176,9 @@ class UNet(_Tracked, nn.Module):
     logits is the reference's, each of them gives a False mask.
 
     Inference only: the native forward folds eval-mode BatchNorm and builds no autograd graph, so
-    calling it in training mode with grad enabled raises (use the reference module to train).
+    calling it in training mode with grad enabled raises (use the reference module to train).  What training
+    keeps a checkpoint by -- the reference's InvoiceLoss on labelled pages -- is computed on the device by
+    ``score`` / ``score_logits`` (with mask IoU and a threshold sweep), see ``metrics.Score``.
     """
 
     def __init__(self, n_channels: int = 3, n_classes: int = 3, compute_dtype: str | None = None,
@@ -347,6 +349,33 @@ class UNet(_Tracked, nn.Module):
         om, ob = out if out is not None else (None, None)
         _, m, boxes = self._run(x, False, kind, want_boxes=True, out_masks=om, out_boxes=ob)
         return boxes if masks is None else (m, boxes)
+
+    def score_logits(self, logits: torch.Tensor, target: torch.Tensor, sweep=None):
+        """Score logits [N, n_classes, H, W] (e.g. ``model(x)``) against ground-truth masks on the device
+        (unet_score): ``target`` is a device tensor, fp32 NCHW with values in [0, 1] (what dataset.py:33-34
+        hands the loss) or uint8 NHWC read as v / 255 (the .npy mask files as stored).  Returns a
+        ``metrics.Score``: the reference's InvoiceLoss / Dice / focal means (train.py:18-59), per-field IoU at
+        the model's thresholds and, with ``sweep`` = up to 64 ascending probabilities, IoU at each of them.
+        Only 64 bytes per (image, field) (and the sweep histogram) are copied to the host; that copy
+        synchronises."""
+        from .metrics import Score
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.shape[1] != self.n_classes:
+            raise RuntimeError(f"score_logits expects logits [N, {self.n_classes}, H, W]")
+        h = self.native_handle(logits.device)
+        logits = logits.detach()
+        if logits.dtype != torch.float32 or not logits.is_contiguous():
+            logits = logits.to(torch.float32).contiguous()
+        target = target.detach().contiguous()
+        probs = None if sweep is None else [float(p) for p in sweep]
+        with torch.cuda.device(logits.device):
+            entries, hist = h.score(logits, target, torch.cuda.current_stream(logits.device).cuda_stream,
+                                    sweep=probs)
+        return Score(entries.cpu().numpy(), None if hist is None else hist.cpu().numpy(), probs)
+
+    def score(self, x: torch.Tensor, target: torch.Tensor, sweep=None):
+        """Forward + ``score_logits`` on one stream: the logits never leave the device."""
+        logits, _ = self._run(x, True, native.MASK_NONE)
+        return self.score_logits(logits, target, sweep)
 
     def preprocess(self, img: torch.Tensor, size: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
         """inference.py:62-64 + :30-44 on the device: a photo as uint8 [H, W, 3] (RGB) or

@@ -47,6 +47,19 @@ class BlockConfig(ctypes.Structure):
     _fields_ = [("in_ch", ctypes.c_int), ("out_ch", ctypes.c_int), ("dtype", ctypes.c_int), ("device", ctypes.c_int)]
 
 
+class ScoreEntry(ctypes.Structure):
+    """unet_score_entry: 64 bytes per (image, field)."""
+    _fields_ = [("sum_p", ctypes.c_double), ("sum_t", ctypes.c_double), ("sum_pt", ctypes.c_double),
+                ("sum_focal", ctypes.c_double), ("n_pred", ctypes.c_int64), ("n_tgt", ctypes.c_int64),
+                ("n_both", ctypes.c_int64), ("n_px", ctypes.c_int64)]
+
+
+# the same record as a numpy structured dtype (metrics.Score holds an [N, C] array of it)
+SCORE_DTYPE = np.dtype([(name, "<f8" if ct is ctypes.c_double else "<i8") for name, ct in ScoreEntry._fields_])
+TGT_F32_NCHW, TGT_U8_NHWC = 0, 1
+SCORE_MAX_K = 64
+
+
 def tensor_views(state_dict):
     """state_dict (name -> torch.Tensor / np.ndarray, any device) -> (TensorView array, arrays to keep alive):
     floating tensors as contiguous host fp32 (numpy has no bfloat16: a model cast with .to(torch.bfloat16)
@@ -79,6 +92,9 @@ SIGNATURES = {
     "unet_forward_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "unet_preprocess": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "unet_crop_stats": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp]),
+    "unet_score_reserve": (_i, [_vp, _i, _i, _i, _i]),
+    "unet_score": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp,
+                        ctypes.POINTER(ctypes.c_float), _i, _vp, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -250,6 +266,45 @@ class Handle:
         with self.lock:
             check(self.lib.unet_preprocess(self._h, img.data_ptr(), ih, iw, c, out.data_ptr(),
                                            out.shape[1], out.shape[2], stream), "unet_preprocess")
+
+    def score_reserve(self, n: int, h: int, w: int, k: int = 0) -> None:
+        """unet_score_reserve: size the score scratch for up to n images of h x w and k sweep candidates."""
+        with self.lock:
+            check(self.lib.unet_score_reserve(self._h, n, h, w, k), "unet_score_reserve")
+
+    def score(self, logits: torch.Tensor, target: torch.Tensor, stream: int, thresholds=None, sweep=None):
+        """unet_score: logits fp32 [N, C, H, W] against target fp32 [N, C, H, W] or uint8 [N, H, W, C] (device,
+        contiguous).  Returns (entries, hist): device uint8 [N, C, 64] holding one ScoreEntry per (image,
+        field), and device int64 [N, C, 2, K + 1] or None without ``sweep`` (K ascending probabilities)."""
+        if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
+            raise ValueError("logits must be a contiguous float32 [N, C, H, W] device tensor")
+        n, c, h, w = logits.shape
+        if target.dtype == torch.float32:
+            kind, shape = TGT_F32_NCHW, (n, c, h, w)
+        elif target.dtype == torch.uint8:
+            kind, shape = TGT_U8_NHWC, (n, h, w, c)
+        else:
+            raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
+        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != logits.device:
+            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {logits.device}")
+        thr = None
+        if thresholds is not None:
+            if len(thresholds) < c:
+                raise ValueError(f"thresholds needs {c} values")
+            thr = (ctypes.c_float * c)(*[float(t) for t in list(thresholds)[:c]])
+        probs, k, hist = None, 0, None
+        if sweep is not None:
+            k = len(sweep)
+            if not 1 <= k <= SCORE_MAX_K:
+                raise ValueError(f"sweep needs 1..{SCORE_MAX_K} probabilities, got {k}")
+            probs = (ctypes.c_float * k)(*[float(p) for p in sweep])
+            hist = torch.empty((n, c, 2, k + 1), device=logits.device, dtype=torch.int64)
+        entries = torch.empty((n, c, ctypes.sizeof(ScoreEntry)), device=logits.device, dtype=torch.uint8)
+        with self.lock:
+            check(self.lib.unet_score(self._h, logits.data_ptr(), target.data_ptr(), kind, n, c, h, w, thr,
+                                      entries.data_ptr(), probs, k, None if hist is None else hist.data_ptr(),
+                                      stream), "unet_score")
+        return entries, hist
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
                       mask_kind: int, stream: int, layout: int = LAYOUT_NCHW) -> list:
