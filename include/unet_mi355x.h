@@ -16,7 +16,7 @@
  *     caller's HIP stream (hipStream_t passed as void*), with no hidden synchronisation
  *     except inside unet_load_weights / unet_reserve (allocation + upload) and the first
  *     unet_preprocess of a new photo geometry (coefficient upload), and unet_score_reserve or a
- *     unet_score whose scratch is too small (allocation).  unet_forward never
+ *     unet_score whose scratch is too small (allocation; unet_loss_reserve / unet_loss_grad alike).  unet_forward never
  *     allocates: size the workspace with unet_reserve first.
  *   - a handle owns one workspace.  Calls on it must not overlap on the host (serialise them;
  *     the Python wrapper holds a lock).  On the device, a call issued on a different stream than
@@ -38,7 +38,7 @@ extern "C" {
                                  5: unet_photo_graph_set_masks (the masks copy is its own node); UNET_DTYPE_F32 as
                                     three bf16 terms, UNET_DTYPE_F32_EXACT the exact-fp32 MFMA
                                     (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
-                                    UNET_TGT_*) */
+                                    UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config) */
 
 /* error codes */
 #define UNET_OK 0
@@ -298,6 +298,36 @@ int unet_score_reserve(unet_handle* h, int N, int H, int W, int K);
 int unet_score(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
                const float* thresholds, unet_score_entry* entries, const float* sweep_probs, int K, int64_t* hist,
                void* hip_stream);
+
+/* The differentiable half of the same loss: what train.py:137-142 does with a batch of logits
+ * (loss = criterion(logits, mask); loss.backward()).  InvoiceLoss (train.py:49-59; gamma = 2, as in unet_score) as
+ * one device fp32 scalar, and its gradient at the logits.
+ *   loss = dice_weight * mean over (n, c) of 1 - (2 sum_pt + smooth) / (sum_p + sum_t + smooth)
+ *        + focal_weight * focal_alpha * sum of sum_focal / (N C H W)
+ * from the sums of unet_score (fp64, bitwise the entries unet_score writes for the same tensors).  The gradient is
+ * autograd's backward of the reference module in fp32, op by op on the element chain above, so the clamp of
+ * train.py:41 passes or cuts an element's focal gradient where the reference does; the Dice branch's per-plane
+ * coefficients are formed in fp64.  A NaN logit makes the loss, its own gradient and the gradient of its whole
+ * (n, c) plane NaN, as torch does. */
+typedef struct unet_loss_config {
+  float dice_weight, focal_weight, focal_alpha, smooth;   /* the reference: 0.85, 0.15, 0.8, 1.0 */
+} unet_loss_config;
+
+/* Size the handle's loss scratch (its own allocation: unet_workspace_bytes, unet_reserve and the score scratch are
+ * unaffected) for losses of up to N images of H x W with up to 4 classes.  Allocating waits for the handle's queued
+ * work. */
+int unet_loss_reserve(unet_handle* h, int N, int H, int W);
+
+/* logits: device fp32 NCHW [N][C][H][W], C in 1..4, any H, W >= 1; target: device, layout per target_kind (UNET_TGT_*).
+ * grad_out: device fp32 scalar, the upstream gradient of the loss, NULL = 1.0.  loss: device fp32 scalar (required).
+ * grad_logits: device fp32 [N][C][H][W], NULL = loss only; it may not be logits itself.
+ * Three or four launches on hip_stream (the two of a score, one block of coefficients, the element-wise gradient),
+ * stream-ordered after the handle's previous call; no host round trip, capturable; needs no weights.  The scratch
+ * grows as unet_score's does: synchronously, or UNET_ESTATE on a stream under capture (call unet_loss_reserve
+ * first).  Bad arguments are UNET_EINVAL before any HIP call. */
+int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
+                   const unet_loss_config* cfg, const float* grad_out, float* loss, float* grad_logits,
+                   void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

@@ -6,6 +6,7 @@
 // mirrors UNet.forward (unet_model.py:55-86).
 #include "unet_internal.h"
 #include "unet_score.h"
+#include "unet_loss.h"
 #include "../../include/unet_mi355x.h"
 
 #include <dlfcn.h>
@@ -154,6 +155,10 @@ struct unet_handle {
   // unet_score_reserve / unet_score
   void* score = nullptr;
   size_t score_bytes = 0;
+  // unet_loss_grad's scratch (the score's slabs of its own step 1, the entries, the gradient coefficients): its own
+  // allocation too, grown by unet_loss_reserve / unet_loss_grad
+  void* loss = nullptr;
+  size_t loss_bytes = 0;
 };
 
 struct unet_graph {
@@ -731,6 +736,9 @@ void free_all(unet_handle* h) {
   if (h->score) (void)hipFree(h->score);
   h->score = nullptr;
   h->score_bytes = 0;
+  if (h->loss) (void)hipFree(h->loss);
+  h->loss = nullptr;
+  h->loss_bytes = 0;
 }
 
 // At least n idle mask-box sync entries (at least 1024: N * n_classes up to 1024 never reallocates).
@@ -1587,6 +1595,68 @@ int unet_score(unet_handle* h, const float* logits, const void* target, int targ
   order_after_last(h, s);
   hipError_t e = launch_score(logits, target, target_kind, N, C, H, W, cuts, h->score, entries, hist, s);
   if (e != hipSuccess) return fail(UNET_EHIP, std::string("score launch: ") + hipGetErrorString(e));
+  mark_done(h, s);
+  return UNET_OK;
+}
+
+namespace {
+int loss_geometry(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
+  if ((long long)N * kMaxClasses * score_spans((long long)H * W) > 0x7FFFFFFFLL)
+    return fail(UNET_EINVAL, "N x H x W too large for one loss");
+  return UNET_OK;
+}
+// a loss scratch of at least `need` bytes
+int grow_loss(unet_handle* h, size_t need) {
+  if (need <= h->loss_bytes) return UNET_OK;
+  if (h->loss) {
+    drain(h);   // queued losses may still read the old scratch
+    (void)hipFree(h->loss);
+    h->loss = nullptr;
+    h->loss_bytes = 0;
+  }
+  hipError_t e = hipMalloc(&h->loss, need);
+  if (e != hipSuccess) {
+    h->loss = nullptr;
+    return fail(UNET_ENOMEM, std::string("loss scratch hipMalloc: ") + hipGetErrorString(e));
+  }
+  h->loss_bytes = need;
+  return UNET_OK;
+}
+}  // namespace
+
+int unet_loss_reserve(unet_handle* h, int N, int H, int W) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  const int rc = loss_geometry(N, H, W);
+  if (rc) return rc;
+  DeviceGuard g(h->cfg.device);
+  return grow_loss(h, loss_scratch_bytes((long long)N * kMaxClasses, (long long)H * W));
+}
+
+int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
+                   const unet_loss_config* cfg, const float* grad_out, float* loss, float* grad_logits, void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!logits || !target || !cfg || !loss) return fail(UNET_EINVAL, "logits, target, cfg and loss must not be NULL");
+  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
+  if (target_kind != UNET_TGT_F32_NCHW && target_kind != UNET_TGT_U8_NHWC)
+    return fail(UNET_EINVAL, "target_kind must be UNET_TGT_F32_NCHW or UNET_TGT_U8_NHWC");
+  int rc = loss_geometry(N, H, W);
+  if (rc) return rc;
+  if (grad_logits == logits) return fail(UNET_EINVAL, "grad_logits must not alias logits");
+  const LossParams prm{cfg->dice_weight, cfg->focal_weight, cfg->focal_alpha, cfg->smooth};
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t need = loss_scratch_bytes((long long)N * C, (long long)H * W);
+  if (need > h->loss_bytes) {
+    if (stream_capturing(h, s))
+      return fail(UNET_ESTATE, "loss scratch too small on a capturing stream: call unet_loss_reserve first");
+    rc = grow_loss(h, need);
+    if (rc) return rc;
+  }
+  order_after_last(h, s);
+  hipError_t e = launch_loss(logits, target, target_kind, N, C, H, W, prm, grad_out, loss, grad_logits, h->loss, s);
+  if (e != hipSuccess) return fail(UNET_EHIP, std::string("loss launch: ") + hipGetErrorString(e));
   mark_done(h, s);
   return UNET_OK;
 }

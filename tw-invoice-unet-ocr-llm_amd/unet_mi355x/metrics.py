@@ -1,10 +1,16 @@
 """Host side of the device scoring (unet_score, include/unet_mi355x.h): the reference's training loss
 (InvoiceLoss, train.py:18-59), Dice, mask IoU and the threshold sweep, assembled in float64 from the 64-byte
-entries the device returns per (image, field).  Pure numpy: nothing here needs a GPU.
+entries the device returns per (image, field) -- pure numpy, nothing there needs a GPU -- and ``InvoiceLoss``, the
+same loss as a criterion: a device scalar with a gradient at the logits (unet_loss_grad).
 """
 from __future__ import annotations
 
+import threading
+
 import numpy as np
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
 
 # unet_score_entry (native.ScoreEntry is the same record as a ctypes struct)
 ENTRY_DTYPE = np.dtype([("sum_p", "<f8"), ("sum_t", "<f8"), ("sum_pt", "<f8"), ("sum_focal", "<f8"),
@@ -122,3 +128,94 @@ class Score:
     def best_thresholds(self) -> np.ndarray:
         """Per class, the candidate probability of the highest pooled IoU (ties: the lowest probability)."""
         return self.probs[np.argmax(self.sweep_iou(), axis=1)]
+
+
+# ---------------------------------------------------------------- the loss as a criterion
+class _InvoiceLossFn(torch.autograd.Function):
+    """loss = InvoiceLoss(pred, target) on the device.  The gradient at the logits is computed in forward (upstream
+    1, one more launch over tensors the loss has just read) and kept; backward multiplies it by the upstream
+    scalar on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, crit, want_grad):
+        loss, grad = crit.loss_and_grad(pred, target, want_grad=want_grad)
+        if want_grad:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return grad * grad_out, None, None, None
+
+
+class InvoiceLoss(nn.Module):
+    """train.InvoiceLoss (train.py:49-59) on the device: ``criterion(logits, mask)`` returns a 0-dim fp32 device
+    tensor, and ``loss.backward()`` leaves in ``logits.grad`` what the reference's autograd leaves there (fp32, op
+    by op).  ``pred``: fp32 logits [N, C, H, W] (C <= 4) on a ROCm device; ``target``: fp32
+    [N, C, H, W] with values in [0, 1], or uint8 [N, H, W, C] read as v / 255 (the .npy masks as stored).  The
+    target gets no gradient.  gamma is 2 (the kernels square); anything else raises ValueError.  There is no CPU
+    fallback."""
+
+    def __init__(self, dice_weight=0.85, focal_weight=0.15, focal_alpha=0.8, gamma=2.0):
+        super().__init__()
+        if float(gamma) != 2.0:
+            raise ValueError(f"unet_mi355x.InvoiceLoss supports gamma = 2 only (the reference's setting), got {gamma}")
+        self.dw, self.fw, self.alpha, self.gamma = float(dice_weight), float(focal_weight), float(focal_alpha), 2.0
+        self.smooth = 1.0   # MultiLabelDiceLoss's default, which InvoiceLoss does not expose
+        self._handles = {}
+        self._lock = threading.Lock()
+
+    @property
+    def weights(self):
+        """(dice_weight, focal_weight, focal_alpha, smooth): unet_loss_config."""
+        return self.dw, self.fw, self.alpha, self.smooth
+
+    def __getstate__(self):   # copies and pickles start without native handles
+        state = self.__dict__.copy()
+        state["_handles"], state["_lock"] = {}, None
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._lock = threading.Lock()
+
+    def _handle(self, device: torch.device):
+        """This criterion's weightless native handle for ``device``."""
+        from . import native
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        with self._lock:
+            h = self._handles.get(idx)
+            if h is None:
+                h = self._handles[idx] = native.Handle(3, 4, "fp32", idx)
+        return h
+
+    @staticmethod
+    def check_pred(pred):
+        if not isinstance(pred, torch.Tensor) or pred.dim() != 4 or not 1 <= pred.shape[1] <= 4:
+            raise RuntimeError("InvoiceLoss expects logits [N, C, H, W] with C in 1..4")
+        if pred.device.type != "cuda":
+            raise RuntimeError("unet_mi355x: InvoiceLoss runs only on a ROCm GPU tensor "
+                               f"(got device {pred.device}); there is no CPU fallback")
+
+    def loss_and_grad(self, pred, target, want_grad=True, handle=None):
+        """(loss, gradient at the logits or None) as device tensors, outside autograd: what ``forward`` and
+        ``UNet.loss_grad`` run.  ``handle``: the native handle to run on (default: this criterion's own)."""
+        self.check_pred(pred)
+        if not isinstance(target, torch.Tensor):
+            raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
+        h = handle if handle is not None else self._handle(pred.device)
+        with torch.cuda.device(pred.device):
+            return h.loss_grad(pred.detach().contiguous(), target.detach().contiguous(),
+                               torch.cuda.current_stream(pred.device).cuda_stream, self.weights, want_grad=want_grad)
+
+    def forward(self, pred, target):
+        self.check_pred(pred)
+        want = bool(pred.requires_grad and torch.is_grad_enabled())
+        return _InvoiceLossFn.apply(pred, target, self, want)
+
+    def close(self):
+        for h in self._handles.values():
+            h.close()
+        self._handles.clear()

@@ -178,7 +178,8 @@ class UNet(_Tracked, nn.Module):
     Inference only: the native forward folds eval-mode BatchNorm and builds no autograd graph, so
     calling it in training mode with grad enabled raises (use the reference module to train).  What training
     keeps a checkpoint by -- the reference's InvoiceLoss on labelled pages -- is computed on the device by
-    ``score`` / ``score_logits`` (with mask IoU and a threshold sweep), see ``metrics.Score``.
+    ``score`` / ``score_logits`` (with mask IoU and a threshold sweep), see ``metrics.Score``; the same loss as a
+    device scalar with its gradient at the logits by ``loss_grad``, see ``metrics.InvoiceLoss``.
     """
 
     def __init__(self, n_channels: int = 3, n_classes: int = 3, compute_dtype: str | None = None,
@@ -376,6 +377,18 @@ class UNet(_Tracked, nn.Module):
         """Forward + ``score_logits`` on one stream: the logits never leave the device."""
         logits, _ = self._run(x, True, native.MASK_NONE)
         return self.score_logits(logits, target, sweep)
+
+    def loss_grad(self, x: torch.Tensor, target: torch.Tensor, criterion=None):
+        """Forward + InvoiceLoss + its gradient at the logits on one stream (unet_loss_grad), the companion of
+        ``score``: returns (loss, grad_logits), a 0-dim fp32 device tensor and fp32 [N, n_classes, H, W].
+        ``criterion``: a ``metrics.InvoiceLoss`` whose weights to use (default: the reference's).  The forward
+        itself stays inference-only; the gradient is the first operator of a backward pass, not the whole of it."""
+        from .metrics import InvoiceLoss
+        crit = criterion if criterion is not None else InvoiceLoss()
+        if not isinstance(crit, InvoiceLoss):
+            raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
+        logits, _ = self._run(x, True, native.MASK_NONE)
+        return crit.loss_and_grad(logits, target, handle=self.native_handle(logits.device))
 
     def preprocess(self, img: torch.Tensor, size: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
         """inference.py:62-64 + :30-44 on the device: a photo as uint8 [H, W, 3] (RGB) or

@@ -60,6 +60,12 @@ TGT_F32_NCHW, TGT_U8_NHWC = 0, 1
 SCORE_MAX_K = 64
 
 
+class LossConfig(ctypes.Structure):
+    """unet_loss_config: InvoiceLoss's weights (train.py:49-59; gamma is 2) and the Dice smooth term."""
+    _fields_ = [("dice_weight", ctypes.c_float), ("focal_weight", ctypes.c_float), ("focal_alpha", ctypes.c_float),
+                ("smooth", ctypes.c_float)]
+
+
 def tensor_views(state_dict):
     """state_dict (name -> torch.Tensor / np.ndarray, any device) -> (TensorView array, arrays to keep alive):
     floating tensors as contiguous host fp32 (numpy has no bfloat16: a model cast with .to(torch.bfloat16)
@@ -95,6 +101,8 @@ SIGNATURES = {
     "unet_score_reserve": (_i, [_vp, _i, _i, _i, _i]),
     "unet_score": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp,
                         ctypes.POINTER(ctypes.c_float), _i, _vp, _vp]),
+    "unet_loss_reserve": (_i, [_vp, _i, _i, _i]),
+    "unet_loss_grad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(LossConfig), _vp, _vp, _vp, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -305,6 +313,52 @@ class Handle:
                                       entries.data_ptr(), probs, k, None if hist is None else hist.data_ptr(),
                                       stream), "unet_score")
         return entries, hist
+
+    def loss_reserve(self, n: int, h: int, w: int) -> None:
+        """unet_loss_reserve: size the loss scratch for up to n images of h x w."""
+        with self.lock:
+            check(self.lib.unet_loss_reserve(self._h, n, h, w), "unet_loss_reserve")
+
+    def loss_grad(self, logits: torch.Tensor, target: torch.Tensor, stream: int, weights=(0.85, 0.15, 0.8, 1.0),
+                  grad_out: torch.Tensor | None = None, want_grad: bool = True,
+                  loss: torch.Tensor | None = None, grad: torch.Tensor | None = None):
+        """unet_loss_grad: InvoiceLoss of logits fp32 [N, C, H, W] against target fp32 [N, C, H, W] or uint8
+        [N, H, W, C] (device, contiguous) with ``weights`` = (dice_weight, focal_weight, focal_alpha, smooth).
+        Returns (loss, grad): a 0-dim fp32 device tensor and the gradient at the logits, fp32 [N, C, H, W], scaled by
+        ``grad_out`` (a one-element fp32 device tensor, None = 1), or None without ``want_grad``.  ``loss`` /
+        ``grad``: caller-owned outputs to fill (e.g. the fixed buffers of a captured call)."""
+        if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
+            raise ValueError("logits must be a contiguous float32 [N, C, H, W] device tensor")
+        n, c, h, w = logits.shape
+        if target.dtype == torch.float32:
+            kind, shape = TGT_F32_NCHW, (n, c, h, w)
+        elif target.dtype == torch.uint8:
+            kind, shape = TGT_U8_NHWC, (n, h, w, c)
+        else:
+            raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
+        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != logits.device:
+            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {logits.device}")
+        if grad_out is not None and (grad_out.dtype != torch.float32 or grad_out.numel() != 1 or
+                                     grad_out.device != logits.device):
+            raise ValueError(f"grad_out must be a one-element float32 tensor on {logits.device}")
+        if loss is None:
+            loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        elif loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != logits.device:
+            raise ValueError(f"loss must be a one-element float32 tensor on {logits.device}")
+        if not want_grad:
+            grad = None
+        elif grad is None:
+            grad = torch.empty((n, c, h, w), device=logits.device, dtype=torch.float32)
+        elif (grad.dtype != torch.float32 or tuple(grad.shape) != (n, c, h, w) or not grad.is_contiguous() or
+              grad.device != logits.device):
+            raise ValueError(f"grad must be a contiguous float32 tensor of shape {(n, c, h, w)} on {logits.device}")
+        cfg = LossConfig(*[float(v) for v in weights])
+        with self.lock:
+            check(self.lib.unet_loss_grad(self._h, logits.data_ptr(), target.data_ptr(), kind, n, c, h, w,
+                                          ctypes.byref(cfg), None if grad_out is None else grad_out.data_ptr(),
+                                          loss.data_ptr(), None if grad is None else grad.data_ptr(), stream),
+                  "unet_loss_grad")
+        return loss, grad
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
                       mask_kind: int, stream: int, layout: int = LAYOUT_NCHW) -> list:
