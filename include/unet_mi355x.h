@@ -38,7 +38,8 @@ extern "C" {
                                  5: unet_photo_graph_set_masks (the masks copy is its own node); UNET_DTYPE_F32 as
                                     three bf16 terms, UNET_DTYPE_F32_EXACT the exact-fp32 MFMA
                                     (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
-                                    UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config) */
+                                    UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config; then
+                                    unet_head_reserve, unet_head_forward, unet_head_backward) */
 
 /* error codes */
 #define UNET_OK 0
@@ -328,6 +329,40 @@ int unet_loss_reserve(unet_handle* h, int N, int H, int W);
 int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
                    const unet_loss_config* cfg, const float* grad_out, float* loss, float* grad_logits,
                    void* hip_stream);
+
+/* The output head on its own: out_conv = Conv2d(64, C, 1) (unet_model.py:50) forward and backward over a stored
+ * feature map -- what fine-tuning the head on a frozen backbone needs (train.py:137-142 restricted to out_conv).
+ *   feat: device fp32 NCHW [N][64][H][W] (DoubleConv's output);  w: device fp32 [C][64], the memory of a contiguous
+ *   Conv2d(64, C, 1).weight;  b: device fp32 [C].  w and b are the caller's (e.g. torch parameters an optimizer
+ *   owns): these calls need no weights loaded into the handle.  C in 1..4, any H, W >= 1; 64-bit indices.
+ * Forward:  logits[n][c][p] = b[c] + sum_k w[c][k] feat[n][k][p], one fp32 fmaf chain from the bias, k ascending:
+ *   bitwise independent of pointer alignment, of N and of the image's place in the batch.
+ * Backward, from feat, grad_logits [N][C][H][W] and w:
+ *   grad_w[c][k] = sum_{n,p} g[n][c][p] feat[n][k][p],  grad_b[c] = sum_{n,p} g[n][c][p]: products and sums in fp64
+ *     over a summation tree that depends on (N, H, W) only, rounded to fp32 once; two launches (per-block partials
+ *     stored to the scratch, then a fixed-order sum), no atomics: bitwise reproducible.
+ *   grad_feat[n][k][p] = sum_c w[c][k] g[n][c][p]: the product of c = 0, then fp32 fmaf, c ascending.
+ * IEEE propagation, nothing special-cased: a NaN feature reaches the logits of its pixel and grad_w[:, k] of its
+ * channel only; a NaN gradient reaches grad_w[c][:], grad_b[c] of its class and grad_feat of its pixel only.
+ * A feature channel that is zero everywhere gives grad_w[:, k] == 0.0 exactly (finite gradients). */
+
+/* Size the handle's head scratch (its own allocation: unet_workspace_bytes, unet_reserve, the score and the loss
+ * scratch are unaffected) for backward calls of up to N images of H x W with up to 4 classes.  Allocating waits
+ * for the handle's queued work. */
+int unet_head_reserve(unet_handle* h, int N, int H, int W);
+
+/* One launch on hip_stream, stream-ordered after the handle's previous call; capturable.  logits: device fp32
+ * [N][C][H][W]; it may not be feat.  Bad arguments are UNET_EINVAL before any HIP call. */
+int unet_head_forward(unet_handle* h, const float* feat, const float* w, const float* b, float* logits,
+                      int N, int C, int H, int W, void* hip_stream);
+
+/* grad_w [C][64] and grad_b [C] come as a pair (both or both NULL); grad_feat [N][64][H][W] may be NULL; not all
+ * three.  grad_feat may not be feat or grad_logits.  Up to three launches on hip_stream, stream-ordered after the
+ * handle's previous call; no host round trip, capturable.  The scratch grows as unet_score's does: synchronously,
+ * or UNET_ESTATE on a stream under capture (call unet_head_reserve first).  Bad arguments are UNET_EINVAL before
+ * any HIP call. */
+int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w,
+                       float* grad_w, float* grad_b, float* grad_feat, int N, int C, int H, int W, void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

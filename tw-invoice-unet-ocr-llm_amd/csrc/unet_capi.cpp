@@ -7,6 +7,7 @@
 #include "unet_internal.h"
 #include "unet_score.h"
 #include "unet_loss.h"
+#include "unet_head.h"
 #include "../../include/unet_mi355x.h"
 
 #include <dlfcn.h>
@@ -159,6 +160,10 @@ struct unet_handle {
   // allocation too, grown by unet_loss_reserve / unet_loss_grad
   void* loss = nullptr;
   size_t loss_bytes = 0;
+  // unet_head_backward's slabs (fp64 partials of grad_w / grad_b): its own allocation too, grown by
+  // unet_head_reserve / unet_head_backward
+  void* head = nullptr;
+  size_t head_bytes = 0;
 };
 
 struct unet_graph {
@@ -739,6 +744,9 @@ void free_all(unet_handle* h) {
   if (h->loss) (void)hipFree(h->loss);
   h->loss = nullptr;
   h->loss_bytes = 0;
+  if (h->head) (void)hipFree(h->head);
+  h->head = nullptr;
+  h->head_bytes = 0;
 }
 
 // At least n idle mask-box sync entries (at least 1024: N * n_classes up to 1024 never reallocates).
@@ -1657,6 +1665,89 @@ int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int 
   order_after_last(h, s);
   hipError_t e = launch_loss(logits, target, target_kind, N, C, H, W, prm, grad_out, loss, grad_logits, h->loss, s);
   if (e != hipSuccess) return fail(UNET_EHIP, std::string("loss launch: ") + hipGetErrorString(e));
+  mark_done(h, s);
+  return UNET_OK;
+}
+
+namespace {
+int head_geometry(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
+  if ((long long)N * head_tiles((long long)H * W) > 0x7FFFFFFFLL)
+    return fail(UNET_EINVAL, "N x H x W too large for one head call");
+  return UNET_OK;
+}
+// a head scratch of at least `need` bytes
+int grow_head(unet_handle* h, size_t need) {
+  if (need <= h->head_bytes) return UNET_OK;
+  if (h->head) {
+    drain(h);   // a queued backward may still read the old slabs
+    (void)hipFree(h->head);
+    h->head = nullptr;
+    h->head_bytes = 0;
+  }
+  hipError_t e = hipMalloc(&h->head, need);
+  if (e != hipSuccess) {
+    h->head = nullptr;
+    return fail(UNET_ENOMEM, std::string("head scratch hipMalloc: ") + hipGetErrorString(e));
+  }
+  h->head_bytes = need;
+  return UNET_OK;
+}
+}  // namespace
+
+int unet_head_reserve(unet_handle* h, int N, int H, int W) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  const int rc = head_geometry(N, H, W);
+  if (rc) return rc;
+  DeviceGuard g(h->cfg.device);
+  return grow_head(h, head_scratch_bytes(N, (long long)H * W, kMaxClasses));
+}
+
+int unet_head_forward(unet_handle* h, const float* feat, const float* w, const float* b, float* logits, int N, int C,
+                      int H, int W, void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!feat || !w || !b || !logits) return fail(UNET_EINVAL, "feat, w, b and logits must not be NULL");
+  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
+  const int rc = head_geometry(N, H, W);
+  if (rc) return rc;
+  if (logits == feat) return fail(UNET_EINVAL, "logits must not alias feat");
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  order_after_last(h, s);
+  hipError_t e = launch_head_forward(feat, w, b, logits, N, C, H, W, s);
+  if (e != hipSuccess) return fail(UNET_EHIP, std::string("head forward launch: ") + hipGetErrorString(e));
+  mark_done(h, s);
+  return UNET_OK;
+}
+
+int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w, float* grad_w,
+                       float* grad_b, float* grad_feat, int N, int C, int H, int W, void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!feat || !grad_logits || !w) return fail(UNET_EINVAL, "feat, grad_logits and w must not be NULL");
+  if ((grad_w == nullptr) != (grad_b == nullptr))
+    return fail(UNET_EINVAL, "grad_w and grad_b come as a pair: both or both NULL");
+  if (!grad_w && !grad_feat) return fail(UNET_EINVAL, "no output: grad_w / grad_b and grad_feat are all NULL");
+  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
+  int rc = head_geometry(N, H, W);
+  if (rc) return rc;
+  if (grad_feat && (grad_feat == feat || grad_feat == grad_logits))
+    return fail(UNET_EINVAL, "grad_feat must not alias feat or grad_logits");
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (grad_w) {
+    const size_t need = head_scratch_bytes(N, (long long)H * W, C);
+    if (need > h->head_bytes) {
+      if (stream_capturing(h, s))
+        return fail(UNET_ESTATE, "head scratch too small on a capturing stream: call unet_head_reserve first");
+      rc = grow_head(h, need);
+      if (rc) return rc;
+    }
+  }
+  order_after_last(h, s);
+  hipError_t e = launch_head_backward(feat, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W, h->head, s);
+  if (e != hipSuccess) return fail(UNET_EHIP, std::string("head backward launch: ") + hipGetErrorString(e));
   mark_done(h, s);
   return UNET_OK;
 }

@@ -581,3 +581,45 @@ def evaluate(img_dir: str, mask_dir: str, checkpoint_path: str, batch: int = 4, 
         with torch.no_grad():
             scores.append(model.score(x, t, sweep))
     return Score.concat(scores)
+
+
+def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: str, epochs: int = 50,
+                  batch: int = 4, lr: float = 1e-3, compute_dtype: str | None = None):
+    """Fit the output head of a checkpoint on a directory of labelled pages (``UNet.fit_head``: a linear probe
+    on frozen features, e.g. for a new invoice layout) and save the result.
+
+    The directory is walked as ``evaluate`` walks it (``labelled_pages``, the same size checks, the uint8 HWC
+    ``.npy`` masks uploaded as stored).  The checkpoint is loaded into a fresh model (not the drop-in's frozen
+    private cache), ``fit_head(x, masks, epochs, batch, lr)`` runs on all pages, and the full 136-key
+    ``state_dict`` -- only ``out_conv.*`` differs from the checkpoint -- is written to ``out_path`` with
+    ``torch.save``.  Returns the per-epoch mean losses."""
+    if not str(DEVICE).startswith("cuda"):
+        raise RuntimeError("unet_mi355x: finetune_head runs on a ROCm GPU; there is no CPU fallback")
+    pages = labelled_pages(img_dir, mask_dir)
+    if not pages:
+        raise ValueError(f"no .jpg / .png pages in {img_dir}")
+    size = None
+    xs, ms = [], []
+    for stem, img_path, mask_path in pages:
+        with Image.open(img_path) as im:
+            a = np.asarray(im.convert("RGB"))
+        m = np.load(mask_path)
+        if size is None:
+            size = a.shape[:2]
+            if size[0] % 16 or size[1] % 16:
+                raise ValueError(f"finetune_head: page {stem} is {size[1]}x{size[0]}; H and W must be divisible by 16")
+        if a.shape[:2] != size:
+            raise ValueError(f"finetune_head: page {stem} is {a.shape[1]}x{a.shape[0]}, the first page "
+                             f"{size[1]}x{size[0]}; all pages must have one size")
+        if m.dtype != np.uint8 or m.shape != size + (len(FIELDS),):
+            raise ValueError(f"finetune_head: mask {mask_path} must be uint8 {size + (len(FIELDS),)}, "
+                             f"got {m.dtype} {m.shape}")
+        xs.append(a.transpose(2, 0, 1).astype(np.float32) / 255.0)
+        ms.append(m)
+    model = load_model(checkpoint_path, compute_dtype)
+    x = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(DEVICE)
+    t = torch.from_numpy(np.ascontiguousarray(np.stack(ms))).to(DEVICE)
+    losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, out_path)
+    model.close()
+    return losses

@@ -7,7 +7,9 @@ works unchanged (inference.py:20-21).  ``forward`` runs the MI355X native path
 weight *container*; they are BN-folded and pre-packed into the native handle the
 first time a forward runs on a device, and again whenever a parameter changes.
 
-There is no CPU / eager fallback: a CPU input raises.
+There is no CPU / eager fallback: a CPU input raises.  The network's own backward pass is not part of this
+project, except for ``out_conv``: ``UNet.features`` / ``head`` / ``fit_head`` fit the output head on frozen
+features (unet_mi355x/head.py).
 """
 from __future__ import annotations
 
@@ -175,8 +177,11 @@ class UNet(_Tracked, nn.Module):
     inf - inf or inf * 0, so there every logit an infinity reaches is NaN: the set of non-finite
     logits is the reference's, each of them gives a False mask.
 
-    Inference only: the native forward folds eval-mode BatchNorm and builds no autograd graph, so
-    calling it in training mode with grad enabled raises (use the reference module to train).  What training
+    The forward is inference only: it folds eval-mode BatchNorm and builds no autograd graph, so calling it
+    in training mode with grad enabled raises (use the reference module to train the network).  The one layer
+    that does train here is the output head: ``features`` returns the 64-channel map ``out_conv`` reads,
+    ``head`` applies ``out_conv`` to it with autograd (``head.head_conv``, native forward and backward), and
+    ``fit_head`` fits ``out_conv`` on labelled pages with the backbone frozen -- a linear probe.  What training
     keeps a checkpoint by -- the reference's InvoiceLoss on labelled pages -- is computed on the device by
     ``score`` / ``score_logits`` (with mask IoU and a threshold sweep), see ``metrics.Score``; the same loss as a
     device scalar with its gradient at the logits by ``loss_grad``, see ``metrics.InvoiceLoss``.
@@ -389,6 +394,112 @@ class UNet(_Tracked, nn.Module):
             raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
         logits, _ = self._run(x, True, native.MASK_NONE)
         return crit.loss_and_grad(logits, target, handle=self.native_handle(logits.device))
+
+    # ------------------------------------------------------------------ the output head on frozen features
+    def features(self, x: torch.Tensor) -> torch.Tensor:
+        """The 64-channel map ``out_conv`` reads (conv1's output, unet_model.py:83), fp32 [N, 64, H, W].
+
+        The fused forward never stores it (conv1.3 and the head are one launch), so it is rebuilt from what
+        the forward does store: ``conv1(cat(u1, c1))`` on the stand-alone DoubleConv, in the model's precision
+        plan and with eval BatchNorm whatever the module's mode -- one forward plus one conv1 block per call,
+        which a frozen backbone pays once per page.  The handle is held from the forward to the fetches, so
+        another thread's forward cannot replace the intermediates in between."""
+        self._check_input(x)
+        if x.device.type != "cuda":
+            raise RuntimeError("unet_mi355x: UNet.features runs only on a ROCm GPU tensor "
+                               f"(got device {x.device}); there is no CPU fallback")
+        n, _, hh, ww = x.shape
+        h = self.native_handle(x.device)
+        x = x.detach()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.to(torch.float32).contiguous()
+        logits = torch.empty((n, self.n_classes, hh, ww), device=x.device, dtype=torch.float32)
+        cat = torch.empty((2, n * 64 * hh * ww), device=x.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        with torch.cuda.device(x.device), h.lock:   # the handle's (re-entrant) lock, forward to last fetch
+            h.reserve(n, hh, ww)
+            h.forward(x, logits, None, native.MASK_NONE, stream)
+            for i, name in enumerate(("u1", "c1")):
+                if h.debug_fetch(name, stream) != cat.shape[1]:
+                    raise RuntimeError(f"unet_mi355x: intermediate {name} is not [N, 64, H, W]")
+                h.debug_fetch_into(name, cat[i], stream)
+        u1c1 = torch.cat([cat[0].view(n, 64, hh, ww), cat[1].view(n, 64, hh, ww)], 1)
+        with torch.no_grad():
+            return self.conv1(u1c1)
+
+    def head(self, feat: torch.Tensor) -> torch.Tensor:
+        """``out_conv`` on a stored feature map (``features``' output): fp32 logits [N, n_classes, H, W], with
+        autograd to ``out_conv.weight`` / ``out_conv.bias`` (and to ``feat`` if it asks) -- ``head.head_conv``."""
+        from .head import head_conv
+        return head_conv(feat, self.out_conv.weight, self.out_conv.bias)
+
+    def fit_head(self, x: torch.Tensor, target: torch.Tensor, epochs: int = 50, batch: int = 4, lr: float = 1e-3,
+                 weight_decay: float = 1e-4, criterion=None, shuffle_seed: int | None = None) -> list:
+        """Fit ``out_conv`` alone on labelled pages, the backbone frozen: a linear probe on frozen features
+        (64 C + C parameters), not train.py's training -- no other parameter moves, BatchNorm runs in eval mode
+        and its statistics stay.  The loop is train.py:119-160 restricted to the head: ``metrics.InvoiceLoss``,
+        AdamW on the two parameters, CosineAnnealingWarmRestarts(T_0=10, T_mult=2) stepped per epoch.
+
+        x: device pages [P, n_channels, H, W]; target: device fp32 [P, C, H, W] in [0, 1] or uint8 [P, H, W, C]
+        (the .npy masks as stored).  The features of all pages are computed once, in chunks of ``batch``, and kept
+        on the device (P x 64 x H x W fp32; RuntimeError if that does not fit).  Batches are consecutive pages, the
+        last one possibly short, reshuffled every epoch with ``shuffle_seed`` (None: never).  Returns the
+        per-epoch mean of the batch losses; the losses are summed on the device and read once per epoch.  The
+        module's train / eval mode is left as found.  The next fused forward uses the new head (the weight
+        signature re-packs the handle)."""
+        from .head import head_conv
+        from .metrics import InvoiceLoss
+        crit = criterion if criterion is not None else InvoiceLoss()
+        if not isinstance(crit, InvoiceLoss):
+            raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
+        if not isinstance(x, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise TypeError("fit_head expects device tensors")
+        if x.device.type != "cuda" or target.device != x.device:
+            raise RuntimeError("unet_mi355x: fit_head runs only on ROCm GPU tensors "
+                               f"(got x on {x.device}, target on {target.device}); there is no CPU fallback")
+        self._check_input(x)
+        if epochs < 1 or batch < 1:
+            raise ValueError("epochs and batch must be >= 1")
+        pages, _, hh, ww = x.shape
+        c = self.n_classes
+        want = (pages, hh, ww, c) if target.dtype == torch.uint8 else (pages, c, hh, ww)
+        if target.dtype not in (torch.uint8, torch.float32) or tuple(target.shape) != want:
+            raise ValueError(f"target must be float32 {(pages, c, hh, ww)} or uint8 {(pages, hh, ww, c)}")
+        weight, bias = self.out_conv.weight, self.out_conv.bias
+        if not (weight.requires_grad and bias.requires_grad):
+            raise RuntimeError("fit_head: out_conv's parameters must require grad")
+        need = pages * 64 * hh * ww * 4
+        with torch.cuda.device(x.device):
+            free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+        if need > free:
+            raise RuntimeError(f"fit_head: the feature cache of {pages} pages of {hh}x{ww} needs {need / 2**30:.2f} "
+                               f"GiB, {free / 2**30:.2f} GiB are free on {x.device}; fit on fewer pages at a time")
+        feats = torch.empty((pages, 64, hh, ww), device=x.device, dtype=torch.float32)
+        for lo in range(0, pages, batch):
+            feats[lo:lo + batch] = self.features(x[lo:lo + batch])
+        target = target.detach().contiguous()
+        opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
+        sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)
+        gen = None if shuffle_seed is None else torch.Generator().manual_seed(int(shuffle_seed))
+        steps = (pages + batch - 1) // batch
+        losses = []
+        with torch.enable_grad():
+            for _ in range(epochs):
+                order = None if gen is None else torch.randperm(pages, generator=gen).to(x.device)
+                total = torch.zeros((), device=x.device, dtype=torch.float32)
+                for lo in range(0, pages, batch):
+                    if order is None:
+                        f, t = feats[lo:lo + batch], target[lo:lo + batch]
+                    else:
+                        f, t = feats[order[lo:lo + batch]], target[order[lo:lo + batch]]
+                    loss = crit(head_conv(f, weight, bias), t)
+                    opt.zero_grad()
+                    loss.backward()
+                    opt.step()
+                    total += loss.detach()
+                losses.append(float(total.item()) / steps)
+                sched.step()
+        return losses
 
     def preprocess(self, img: torch.Tensor, size: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
         """inference.py:62-64 + :30-44 on the device: a photo as uint8 [H, W, 3] (RGB) or

@@ -103,6 +103,9 @@ SIGNATURES = {
                         ctypes.POINTER(ctypes.c_float), _i, _vp, _vp]),
     "unet_loss_reserve": (_i, [_vp, _i, _i, _i]),
     "unet_loss_grad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(LossConfig), _vp, _vp, _vp, _vp]),
+    "unet_head_reserve": (_i, [_vp, _i, _i, _i]),
+    "unet_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "unet_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -359,6 +362,65 @@ class Handle:
                                           loss.data_ptr(), None if grad is None else grad.data_ptr(), stream),
                   "unet_loss_grad")
         return loss, grad
+
+    def head_reserve(self, n: int, h: int, w: int) -> None:
+        """unet_head_reserve: size the head backward's scratch for up to n images of h x w."""
+        with self.lock:
+            check(self.lib.unet_head_reserve(self._h, n, h, w), "unet_head_reserve")
+
+    @staticmethod
+    def _head_operands(feat: torch.Tensor, weight: torch.Tensor):
+        """(n, c, h, w) of a head call: feat fp32 [N, 64, H, W], weight fp32 with C x 64 elements, contiguous."""
+        if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != 64 or not feat.is_contiguous():
+            raise ValueError("feat must be a contiguous float32 [N, 64, H, W] device tensor")
+        if (weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() < 2 or weight.shape[1] != 64
+                or weight.numel() != weight.shape[0] * 64 or weight.device != feat.device):
+            raise ValueError(f"weight must be a contiguous float32 [C, 64] or [C, 64, 1, 1] tensor on {feat.device}")
+        n, _, h, w = feat.shape
+        return n, int(weight.shape[0]), h, w
+
+    @staticmethod
+    def _head_tensor(t: torch.Tensor | None, shape, like: torch.Tensor, what: str) -> torch.Tensor:
+        if t is None:
+            return torch.empty(shape, device=like.device, dtype=torch.float32)
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != like.device:
+            raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {like.device}")
+        return t
+
+    def head_forward(self, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stream: int,
+                     logits: torch.Tensor | None = None) -> torch.Tensor:
+        """unet_head_forward: out_conv on feat fp32 [N, 64, H, W] with weight [C, 64(, 1, 1)] and bias [C] (device,
+        contiguous fp32).  Returns the logits fp32 [N, C, H, W] (``logits``: a caller-owned output to fill)."""
+        n, c, h, w = self._head_operands(feat, weight)
+        bias = self._head_tensor(bias, (c,), feat, "bias")
+        logits = self._head_tensor(logits, (n, c, h, w), feat, "logits")
+        with self.lock:
+            check(self.lib.unet_head_forward(self._h, feat.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                             logits.data_ptr(), n, c, h, w, stream), "unet_head_forward")
+        return logits
+
+    def head_backward(self, feat: torch.Tensor, grad_logits: torch.Tensor, weight: torch.Tensor, stream: int,
+                      want_params: bool = True, want_feat: bool = False, grad_w: torch.Tensor | None = None,
+                      grad_b: torch.Tensor | None = None, grad_feat: torch.Tensor | None = None):
+        """unet_head_backward: from feat, grad_logits fp32 [N, C, H, W] and weight, (grad_w [C, 64], grad_b [C],
+        grad_feat [N, 64, H, W]); the pair is None without ``want_params``, grad_feat without ``want_feat``.
+        ``grad_w`` / ``grad_b`` / ``grad_feat``: caller-owned outputs to fill."""
+        n, c, h, w = self._head_operands(feat, weight)
+        grad_logits = self._head_tensor(grad_logits, (n, c, h, w), feat, "grad_logits")
+        if not (want_params or want_feat):
+            raise ValueError("head_backward: nothing to compute")
+        if want_params:
+            grad_w = self._head_tensor(grad_w, (c, 64), feat, "grad_w")
+            grad_b = self._head_tensor(grad_b, (c,), feat, "grad_b")
+        else:
+            grad_w = grad_b = None
+        grad_feat = self._head_tensor(grad_feat, (n, 64, h, w), feat, "grad_feat") if want_feat else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        with self.lock:
+            check(self.lib.unet_head_backward(self._h, feat.data_ptr(), grad_logits.data_ptr(), weight.data_ptr(),
+                                              ptr(grad_w), ptr(grad_b), ptr(grad_feat), n, c, h, w, stream),
+                  "unet_head_backward")
+        return grad_w, grad_b, grad_feat
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
                       mask_kind: int, stream: int, layout: int = LAYOUT_NCHW) -> list:
