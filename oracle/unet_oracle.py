@@ -76,10 +76,18 @@ def unet_forward(sd, x: torch.Tensor, return_intermediates: bool = False):
     return out
 
 
-def masks_from_logits(logits: np.ndarray) -> dict:
-    """inference.py:72-79: sigmoid in fp32, then strict '>' against the fp32 constants."""
+def masks_from_logits(logits: np.ndarray, thresholds=None) -> dict:
+    """inference.py:72-79: sigmoid in fp32, then strict '>' against the fp32 constants.
+
+    ``thresholds`` (optional): one probability per plane of ``logits`` [C, H, W] instead of the three fields'
+    constants (a model of another class count, or with thresholds of its own); the result is then keyed by
+    the class index."""
     prob = torch.sigmoid(torch.from_numpy(np.ascontiguousarray(logits, dtype=np.float32))).numpy()
-    return {k: prob[i] > np.float32(THRESHOLDS[k]) for i, k in enumerate(FIELDS)}
+    if thresholds is None:
+        return {k: prob[i] > np.float32(THRESHOLDS[k]) for i, k in enumerate(FIELDS)}
+    if len(thresholds) < prob.shape[0]:
+        raise ValueError(f"{prob.shape[0]} classes need as many thresholds, got {len(thresholds)}")
+    return {c: prob[c] > np.float32(thresholds[c]) for c in range(prob.shape[0])}
 
 
 def crop_boxes(masks: dict, ow: int, oh: int) -> dict:

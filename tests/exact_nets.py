@@ -104,9 +104,9 @@ def _put_conv_bn(sd: dict, block: str, idx: int, ent: dict) -> None:
     sd[f"{block}.net.{idx + 1}.num_batches_tracked"] = np.array(0, dtype=np.int64)
 
 
-def _ordered(sd: dict, n_channels: int) -> "OrderedDict[str, np.ndarray]":
+def _ordered(sd: dict, n_channels: int, n_classes: int = 3) -> "OrderedDict[str, np.ndarray]":
     out = OrderedDict()
-    for key, shape in syn.unet_shapes(n_channels, 3):
+    for key, shape in syn.unet_shapes(n_channels, n_classes):
         assert tuple(sd[key].shape) == tuple(shape), key
         out[key] = sd[key]
     assert len(out) == len(sd)
@@ -169,13 +169,19 @@ def routing_input(seed: int, n: int, c_in: int, h: int, w: int, bits: int = 4) -
     return rng.integers(0, 2 ** bits, (n, c_in, h, w)).astype(np.float32)
 
 
+# UNet's default thresholds, padded to four classes as native.Handle pads them
+DEFAULT_THRESHOLDS = (0.25, 0.40, 0.30, 0.5)
+
+
+def logit_cut64(thr: float) -> float:
+    """logit(thr) in float64: where sigmoid crosses ``thr`` (the library's unet_logit_cut is the fp32 value below it)."""
+    return float(np.log(thr / (1.0 - thr)))
+
+
 @functools.lru_cache(maxsize=None)
-def routing_state_dict(seed: int, c_in: int) -> "OrderedDict[str, np.ndarray]":
-    """A UNet state_dict that only routes and adds small integers (module docstring).  BatchNorm is the
-    identity of ``exact_fold`` with an integer beta in [0, 2]; ConvTranspose has one +1 per (cout, dy, dx)
-    and bias 0; out_conv has one +1 per class and a negative integer bias, chosen from the float64 run of a
-    32 x 32 probe input so that each class's logits straddle its cut.  The returned arrays are shared
-    (cached): treat them as read-only."""
+def _routing_body(seed: int, c_in: int):
+    """Every layer of a routing network but out_conv, and the generator's state after drawing them (the
+    one-hot head goes on drawing from it).  Shared between the class counts and heads of one (seed, c_in)."""
     rng = np.random.default_rng([seed, c_in, 1])
     sd = {}
     for name, (ci, co) in BLOCKS.items():
@@ -190,23 +196,76 @@ def routing_state_dict(seed: int, c_in: int) -> "OrderedDict[str, np.ndarray]":
         w[src, o, dy, dx] = 1.0
         sd[f"{name}.weight"] = w
         sd[f"{name}.bias"] = np.zeros(co, np.float32)
+    for v in sd.values():
+        v.setflags(write=False)
+    return sd, rng.bit_generator.state
+
+
+def _dense_head_weights(seed: int, c_in: int, n_classes: int) -> np.ndarray:
+    """[n_classes, 64] in {-1, 0, +1}: every channel nonzero in at least one class, the class rows pairwise
+    different, each with both signs.  Its own generator, so the one-hot networks' draws stay what they were."""
+    rng = np.random.default_rng([seed, c_in, n_classes, 11])
+    while True:
+        w = rng.integers(-1, 2, (n_classes, 64))
+        dead = np.flatnonzero(~(w != 0).any(axis=0))
+        w[rng.integers(0, n_classes, dead.size), dead] = rng.choice([-1, 1], dead.size)
+        if all((r > 0).any() and (r < 0).any() for r in w) and len({r.tobytes() for r in w}) == n_classes:
+            return w.astype(np.float32)
+
+
+def routing_state_dict(seed: int, c_in: int, n_classes: int = 3, head: str = "onehot",
+                       thresholds=None) -> "OrderedDict[str, np.ndarray]":
+    """A UNet state_dict that only routes and adds small integers (module docstring).  BatchNorm is the
+    identity of ``exact_fold`` with an integer beta in [0, 2]; ConvTranspose has one +1 per (cout, dy, dx)
+    and bias 0.  out_conv, ``head`` = "onehot": one +1 per class and a negative integer bias, chosen from the
+    float64 run of a 32 x 32 probe input so that each class's logits straddle its cut.  ``head`` = "dense":
+    weights in {-1, 0, +1} over all 64 channels (_dense_head_weights), so that every K slot of the head's dot
+    carries a term, and per class the integer bias that puts 30 .. 70 % of the probe's logits above the class's
+    cut -- that of ``thresholds`` (a tuple of at least n_classes probabilities; default: the model's).  The
+    returned arrays are shared (cached): treat them as read-only."""
+    assert head in ("onehot", "dense") and 1 <= n_classes <= 4
+    thr = None
+    if head == "dense":   # the one-hot head does not read them
+        thr = tuple(float(t) for t in (DEFAULT_THRESHOLDS if thresholds is None else thresholds))[:n_classes]
+        assert len(thr) == n_classes
+    return _routing_state_dict(seed, c_in, n_classes, head, thr)
+
+
+@functools.lru_cache(maxsize=None)
+def _routing_state_dict(seed, c_in, n_classes, head, thr):
+    body, state = _routing_body(seed, c_in)
+    sd = dict(body)
     # out_conv: placeholder, then the probe picks channel and bias
-    sd["out_conv.weight"] = np.zeros((3, 64, 1, 1), np.float32)
-    sd["out_conv.bias"] = np.zeros(3, np.float32)
+    sd["out_conv.weight"] = np.zeros((n_classes, 64, 1, 1), np.float32)
+    sd["out_conv.bias"] = np.zeros(n_classes, np.float32)
     c8 = routing_forward_f64(sd, routing_input(seed, 1, c_in, 32, 32))["c8"][0].reshape(64, -1)
-    # a channel and an integer level t >= 1 that 30 .. 70 % of the channel's probe pixels reach; the logit
-    # c8 - t is then >= 0 (above the cuts -0.41 and -0.85) on that share, and c8 - t - 1 >= -1 (above -1.10)
-    picks = []
-    for c in rng.permutation(64):
-        levels = [t for t in range(1, int(c8[c].max()) + 1) if 0.3 <= (c8[c] >= t).mean() <= 0.7]
-        if levels:
-            picks.append((int(c), levels[len(levels) // 2]))
-    assert len(picks) >= 3, "routing net: conv1.3 has too few lively channels for the head"
-    for k, (c, t) in enumerate(picks[:3]):
-        sd["out_conv.weight"][k, c, 0, 0] = 1.0
-        sd["out_conv.bias"][k] = -float(t + 1 if k == 0 else t)
-    assert np.all(sd["out_conv.bias"] < 0)
-    out = _ordered(sd, c_in)
+    if head == "dense":
+        w = _dense_head_weights(seed, c_in, n_classes)
+        s = w.astype(np.float64) @ c8
+        for k in range(n_classes):
+            first = int(np.floor(logit_cut64(thr[k]))) + 1        # the smallest integer logit above the cut
+            levels = [t for t in np.unique(s[k]).astype(np.int64) if 0.3 <= (s[k] >= t).mean() <= 0.7]
+            assert levels, "routing net: a dense head row whose probe sums do not straddle any level"
+            sd["out_conv.bias"][k] = float(first - levels[len(levels) // 2])   # s >= level  <=>  logit >= first
+            share = float((s[k] + sd["out_conv.bias"][k] > logit_cut64(thr[k])).mean())
+            assert 0.3 <= share <= 0.7, (k, share)
+        sd["out_conv.weight"][:] = w.reshape(n_classes, 64, 1, 1)
+    else:
+        rng = np.random.default_rng()
+        rng.bit_generator.state = state
+        # a channel and an integer level t >= 1 that 30 .. 70 % of the channel's probe pixels reach; the logit
+        # c8 - t is then >= 0 (above the cuts -0.41 and -0.85) on that share, and c8 - t - 1 >= -1 (above -1.10)
+        picks = []
+        for c in rng.permutation(64):
+            levels = [t for t in range(1, int(c8[c].max()) + 1) if 0.3 <= (c8[c] >= t).mean() <= 0.7]
+            if levels:
+                picks.append((int(c), levels[len(levels) // 2]))
+        assert len(picks) >= max(3, n_classes), "routing net: conv1.3 has too few lively channels for the head"
+        for k, (c, t) in enumerate(picks[:n_classes]):
+            sd["out_conv.weight"][k, c, 0, 0] = 1.0
+            sd["out_conv.bias"][k] = -float(t + 1 if k == 0 else t)
+        assert np.all(sd["out_conv.bias"] < 0)
+    out = _ordered(sd, c_in, n_classes)
     for v in out.values():
         v.setflags(write=False)
     return out
@@ -277,12 +336,21 @@ def wide_layer_terms(sd, layer: str, src: np.ndarray):
 
 
 @functools.lru_cache(maxsize=None)
-def routing_reference(seed: int, c_in: int, n: int, h: int, w: int, bits: int = 4, wide_w=None):
+def routing_reference(seed: int, c_in: int, n: int, h: int, w: int, bits: int = 4, wide_w=None,
+                      n_classes: int = 3, head: str = "onehot", thresholds=None, mirror: bool = False):
     """(x, ref): the input and the fp32 oracle's logits and intermediates by ``UNet.intermediate`` name, in
     forward order (u4..u1 and c8a: the oracle's own ops applied to the oracle's own tensors).  ``wide_w`` =
-    (layer, kind): on ``routing_state_dict_wide_w``.  Cached and shared between tests: read-only."""
-    sd = routing_state_dict(seed, c_in) if wide_w is None else routing_state_dict_wide_w(seed, c_in, *wide_w)
+    (layer, kind): on ``routing_state_dict_wide_w``; ``n_classes``, ``head``, ``thresholds``: those of
+    ``routing_state_dict``; ``mirror``: the input flipped left to right.  Cached and shared between tests:
+    read-only."""
+    if wide_w is None:
+        sd = routing_state_dict(seed, c_in, n_classes, head, thresholds)
+    else:
+        assert n_classes == 3 and head == "onehot"
+        sd = routing_state_dict_wide_w(seed, c_in, *wide_w)
     x = routing_input(seed, n, c_in, h, w, bits)
+    if mirror:
+        x = np.ascontiguousarray(x[..., ::-1])
     sdt = {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}
     logits, it = orc.unet_forward(sdt, torch.from_numpy(x), return_intermediates=True)
     with torch.no_grad():
@@ -313,6 +381,11 @@ ROUTING_LARGE = [(7, 3, 2, 512, 512)]
 # carries activations with nonzero hi, mid and lo terms against +-1 weights; a - b + beta stays below 2^24
 ROUTING_WIDE = [(4, 3, 3, 48, 80), (2, 3, 6, 16, 112)]
 WIDE_BITS = 23
+# the class-count tests (tests/test_classes_gpu.py), dense head, 1 / 2 / 4 (and 3) classes at non-default thresholds:
+# the small-batch plan with every tile partial (masks packed per byte); ragged with W % 32 != 0; W % 32 == 0 (the
+# 16 x 32-tile kernels pack a dword per class and row); above the small-batch limit, several such tiles per row
+ROUTING_CLASSES = [(9, 3, 1, 16, 16), (10, 1, 3, 48, 80), (11, 3, 2, 64, 64), (12, 3, 5, 32, 96)]
+CLASS_THRESHOLDS = (0.35, 0.5, 0.1, 0.9)
 
 # tensors a forward stores, in forward order, and the launch (include/unet_mi355x.h order) that writes each
 FORWARD_ORDER = ["c1", "p1", "c2", "p2", "c3", "p3", "c4", "p4", "bn", "u4", "u3", "u2", "c7", "u1", "c8a", "logits"]
@@ -328,6 +401,44 @@ def describe_mismatch(name: str, got: np.ndarray, want: np.ndarray, label: str, 
     bad = np.argwhere(got != want)
     head = "; ".join(f"{tuple(int(i) for i in p)} got {got[tuple(p)]!r} want {want[tuple(p)]!r}" for p in bad[:limit])
     return f"{name}: {len(bad)} of {got.size} elements differ; first (n, c, y, x): {head}; launch: {label}"
+
+
+def first_stored_mismatch(model, logits: np.ndarray, ref: dict, labels: list):
+    """The logits and every tensor the model's last forward stored (``UNet.intermediate``) against ``ref``
+    (routing_reference), bitwise, in forward order: None, or describe_mismatch of the first wrong tensor with the
+    kernel that wrote it.  With up1 fused into conv2.3 (an empty label 19) c7 is never stored: fetching it must
+    raise."""
+    import pytest
+    fused = labels[19] == ""
+    got = {}
+    for k in FORWARD_ORDER[:-1]:
+        if k == "c7" and fused:
+            with pytest.raises(RuntimeError, match="not stored"):
+                model.intermediate(k)
+            continue
+        got[k] = model.intermediate(k).cpu().numpy().reshape(ref[k].shape)
+    got["logits"] = np.asarray(logits)
+    for k in FORWARD_ORDER:
+        if k in got and not np.array_equal(got[k], ref[k]):
+            launch = 18 if (k == "u1" and fused) else LAUNCH_OF[k]
+            return describe_mismatch(k, got[k], ref[k], labels[launch])
+    return None
+
+
+def np_boxes(masks: np.ndarray) -> np.ndarray:
+    """[N, C, H, W] bool -> int32 [N, C, 4] (x_min, y_min, x_max, y_max), -1s for an empty mask."""
+    out = np.full(masks.shape[:2] + (4,), -1, dtype=np.int32)
+    for i in range(masks.shape[0]):
+        for c in range(masks.shape[1]):
+            ys, xs = np.where(masks[i, c])
+            if len(xs):
+                out[i, c] = (xs.min(), ys.min(), xs.max(), ys.max())
+    return out
+
+
+def reference_masks(logits: np.ndarray, thresholds) -> np.ndarray:
+    """[N, C, H, W] logits -> bool masks, the oracle's sigmoid > thresholds[c] in fp32."""
+    return np.stack([np.stack(list(orc.masks_from_logits(np.array(lg), thresholds).values())) for lg in logits])
 
 
 # ------------------------------------------------------------------------------------------------ section 2

@@ -23,7 +23,8 @@ DTYPES = {"fp32": native.DTYPES["fp32"], "mixed": native.DTYPES["mixed"]}
 
 def write_inputs(d, sd, x, thresholds):
     """manifest.txt + weights.bin (the state_dict as raw host tensors) + x.bin, the C host's format."""
-    lines = [" ".join([str(3)] + [repr(float(t)) for t in list(thresholds) + [0.5] * (4 - len(thresholds))])]
+    n_classes = int(np.asarray(sd["out_conv.bias"]).shape[0])
+    lines = [" ".join([str(n_classes)] + [repr(float(t)) for t in list(thresholds) + [0.5] * (4 - len(thresholds))])]
     off = 0
     with open(os.path.join(d, "weights.bin"), "wb") as f:
         for k, v in sd.items():
@@ -64,10 +65,21 @@ def test_c_host_binary_matches_the_header():
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["mixed", "fp32"])
 def test_c_host_forward_equals_python_binding(dtype):
-    sd = {k: np.asarray(v) for k, v in syn.make_state_dict(0, 3, 3, "pretrained").items()}
+    _c_host_equals_python_binding(syn.make_state_dict(0, 3, 3, "pretrained"), 3, (0.25, 0.40, 0.30), dtype)
+
+
+@pytest.mark.gpu
+def test_c_host_forward_four_classes():
+    """The same at 4 classes and thresholds of the caller's: the manifest carries both."""
+    _c_host_equals_python_binding(syn.make_state_dict(5, 3, 4, "structured", out_bias=0.0), 4, (0.35, 0.5, 0.1, 0.9),
+                                  "mixed")
+
+
+def _c_host_equals_python_binding(sd, n_classes, thresholds, dtype):
+    sd = {k: np.asarray(v) for k, v in sd.items()}
     n, hw = 2, 256
     x = syn.invoice_pages(41, n, hw, hw, 3)
-    m = UNet(3, 3, compute_dtype=dtype)
+    m = UNet(3, n_classes, compute_dtype=dtype, thresholds=thresholds)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     m = m.to("cuda:0").eval()
     xd = torch.from_numpy(x).to("cuda:0")

@@ -55,6 +55,102 @@ def test_routing_net_is_exact_and_lively(case):
             assert 0.05 <= share <= 0.95, (c, share)
 
 
+# sha256 (synthetic.state_dict_checksum) of the default routing networks -- 3 classes, one-hot head -- of every
+# (seed, c_in) the bitwise tests use, taken before routing_state_dict learnt class counts and the dense head
+ROUTING_CHECKSUMS = {
+    (0, 3): "2151dffba750b32561f57d1b45d79737129a05c50ca11b227b21e606ed943d9f",
+    (1, 1): "6a416bae79c9693c62ac1171454d4288004e1427bf86b7704cca8f06271c186a",
+    (2, 3): "c39682ecb80657071559892703bbca72aa82da97b4409d9b440cae604ad3b4b1",
+    (3, 1): "7928c805f967c06a1840fe47dfc2858884fbe3012d74bb220ef75675cb7d835f",
+    (4, 3): "5e9807510889fbacc35f4eb4f612fd37f466289b5d7a7377d0322ba2247569d9",
+    (5, 1): "82284f4c5fabb66a8ff37aa09a66af6a8d2d4d1cfb67c74f55d1e36827794706",
+    (6, 3): "1a648b81b3244c675826b56197f9cb611c9d3bb4577d9040dee010808541a393",
+    (7, 3): "8c5170f49588e7943806072ef5a9f131aea6b407200d4a81dbbaa9883f1c15b7",
+    (8, 3): "60f5ee963fa36a10ef20e33324398ec3c290d236a4cf674bb82237818ed9f025",
+}
+
+
+def test_default_routing_nets_are_unchanged():
+    """The 3-class one-hot routing networks are byte for byte what they were before the class count and the
+    dense head became arguments (the generator's draw order is kept), however the defaults are spelt."""
+    from unet_mi355x import synthetic as syn
+    used = {(s, c) for s, c, *_ in en.ROUTING_SMALL + en.ROUTING_RAGGED + [en.ROUTING_FORCED] + en.ROUTING_LARGE}
+    assert used == set(ROUTING_CHECKSUMS)
+    assert not used & {(s, c) for s, c, *_ in en.ROUTING_CLASSES}, "the class-count cases take seeds of their own"
+    for (seed, c_in), want in ROUTING_CHECKSUMS.items():
+        assert syn.state_dict_checksum(en.routing_state_dict(seed, c_in)) == want, (seed, c_in)
+    assert en.routing_state_dict(8, 3, 3, "onehot") is en.routing_state_dict(8, 3)
+    # the other class counts of the one-hot head: the first classes of the same draw
+    sd3 = en.routing_state_dict(8, 3)
+    for ncls in (1, 2, 4):
+        sd = en.routing_state_dict(8, 3, ncls)
+        k = min(ncls, 3)
+        assert sd["out_conv.weight"].shape == (ncls, 64, 1, 1)
+        assert np.array_equal(sd["out_conv.weight"][:k], sd3["out_conv.weight"][:k])
+        assert np.array_equal(sd["out_conv.bias"][:k], sd3["out_conv.bias"][:k])
+        assert all(np.array_equal(sd[key], sd3[key]) for key in sd3 if not key.startswith("out_conv"))
+
+
+CLASS_COUNTS = [1, 2, 3, 4]
+# A cut's distance to the nearest integer, for the thresholds 0.35 / 0.5 / 0.1 / 0.9 of the class-count tests:
+# logit = -0.619 / 0 / -2.197 / +2.197, so 0.38 / 0 / 0.197 / 0.197.  Integer logits therefore keep 0.19 from
+# every cut but that of 0.5, which the integer 0 meets exactly -- a tie that is exact on both sides: the fp32
+# sigmoid of 0 is 0.5, which is not > 0.5, and 0 is not above the library's cut either (asserted below).
+CUT_MARGIN = 0.19
+
+
+@pytest.mark.parametrize("n_classes", CLASS_COUNTS)
+@pytest.mark.parametrize("case", en.ROUTING_CLASSES, ids=str)
+def test_dense_head_routing_net_premises(case, n_classes):
+    """What makes the dense-head networks of tests/test_classes_gpu.py exact in every plan: out_conv in
+    {-1, 0, +1} over all 64 channels (every channel in some class, rows different, both signs), an integer bias
+    that puts 30 .. 70 % of the probe's logits above the class's cut; c8 integer-valued with |v| <= 256 (so the
+    16-bit head's rounding of its B operand changes nothing, and +-1 is a bf16 and an fp16 value); integer
+    logits below 2^24; the float64 forward equal to the fp32 oracle; and no logit near a cut of ANY class
+    (CUT_MARGIN), so that the masks -- also those a kernel would cut at a neighbour's slot -- do not hang on
+    a rounding: the library's ``logit > unet_logit_cut(thr)`` and the oracle's fp32 sigmoid > thr agree."""
+    import torch
+    from unet_mi355x import native
+    seed, c_in, n, h, w = case
+    thr = en.CLASS_THRESHOLDS[:n_classes]
+    sd = en.routing_state_dict(seed, c_in, n_classes, "dense", thr)
+    hw = sd["out_conv.weight"].reshape(n_classes, 64)
+    assert set(np.unique(hw)) <= {-1.0, 0.0, 1.0} and (hw != 0).any(axis=0).all()
+    assert all((r > 0).any() and (r < 0).any() for r in hw)
+    assert len({r.tobytes() for r in hw}) == n_classes
+    assert np.array_equal(sd["out_conv.bias"], np.round(sd["out_conv.bias"]))
+    probe = en.routing_forward_f64(sd, en.routing_input(seed, 1, c_in, 32, 32))["logits"]
+    for c in range(n_classes):
+        share = float((probe[:, c] > en.logit_cut64(thr[c])).mean())
+        assert 0.3 <= share <= 0.7, (c, share)
+    x, ref = en.routing_reference(seed, c_in, n, h, w, n_classes=n_classes, head="dense", thresholds=thr)
+    f64 = en.routing_forward_f64(sd, x)
+    for k in en.FORWARD_ORDER:
+        assert np.array_equal(ref[k].astype(np.float64), f64[k]), k
+        assert np.array_equal(en.bf16_rne(ref[k]), ref[k]) or k == "logits", k
+    c8 = f64["c8"]
+    assert np.array_equal(c8, np.round(c8)) and np.abs(c8).max() <= 256
+    assert np.array_equal(en.bf16_rne(c8.astype(np.float32)), c8) and np.array_equal(en.f16_rne(c8.astype(np.float32)), c8)
+    logits = ref["logits"]
+    assert np.array_equal(logits, np.round(logits)) and np.abs(logits).max() < 2.0 ** 24
+    lib = native.load_library()
+    masks = en.reference_masks(logits, thr)
+    for c in range(n_classes):
+        share = float(masks[:, c].mean())
+        print(f"{case} {n_classes} classes, class {c}: bias {sd['out_conv.bias'][c]:.0f}, logits in "
+              f"[{logits[:, c].min():.0f}, {logits[:, c].max():.0f}], {100 * share:.0f} % above the cut")
+        if h >= 48:
+            assert 0.05 <= share <= 0.95, (c, share)
+        for t in thr:   # every class's cut: a logit compared against the wrong slot is decided as firmly
+            d = np.abs(logits[:, c].astype(np.float64) - en.logit_cut64(t))
+            tie = (logits[:, c] == 0) & (t == 0.5)
+            assert d[~tie].min() >= CUT_MARGIN, (c, t, float(d[~tie].min()))
+            cut = np.float32(lib.unet_logit_cut(np.float32(t)))
+            vals = np.unique(logits[:, c])
+            assert np.array_equal(vals > cut, torch.sigmoid(torch.from_numpy(vals)).numpy() > np.float32(t)), (c, t)
+        assert np.array_equal(masks[:, c], logits[:, c] > np.float32(lib.unet_logit_cut(np.float32(thr[c]))))
+
+
 @pytest.mark.parametrize("case", en.ROUTING_WIDE, ids=str)
 def test_routing_net_on_wide_inputs(case):
     """The routing networks on 23-bit inputs (the fp32 plans' whole-network run): still oracle == float64

@@ -50,19 +50,10 @@ def _check_routing(case, dtype, tag="", bits=4, wide_w=None):
             logits = m(xd)
         torch.cuda.synchronize()
         labels = m.native_handle(torch.device(DEV)).launch_labels_at(n, h, w)
-        fused = labels[19] == ""            # up1 fused into conv2.3 (EPI_UPFUSE): c7 is never stored
-        got = {}
-        for k in en.FORWARD_ORDER[:-1]:
-            if k == "c7" and fused:
-                with pytest.raises(RuntimeError, match="not stored"):
-                    m.intermediate(k)
-                continue
-            got[k] = m.intermediate(k).cpu().numpy().reshape(ref[k].shape)
-        got["logits"] = logits.cpu().numpy()
-        for k in en.FORWARD_ORDER:
-            if k in got and not np.array_equal(got[k], ref[k]):
-                launch = 18 if (k == "u1" and fused) else en.LAUNCH_OF[k]
-                pytest.fail(f"{dtype} {case} {tag}: " + en.describe_mismatch(k, got[k], ref[k], labels[launch]))
+        # logits and every stored tensor (with up1 fused into conv2.3, EPI_UPFUSE, c7 is never stored)
+        bad = en.first_stored_mismatch(m, logits.cpu().numpy(), ref, labels)
+        if bad:
+            pytest.fail(f"{dtype} {case} {tag}: {bad}")
         ref_masks = np.stack([np.stack([orc.masks_from_logits(np.array(ref["logits"][i]))[f] for f in orc.FIELDS])
                               for i in range(n)])
         with torch.no_grad():
