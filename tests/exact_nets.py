@@ -13,6 +13,10 @@ addressing, packing, border, concat or pixel-shuffle error shows as a wrong valu
   wide_block          one DoubleConv whose first conv carries wide integers (the three-term fp32 plan's
                       hi / mid / lo products), the second being a centre-tap identity
 
+The rounding networks (section 3; tests/test_rounding_cpu.py, tests/test_rounding_gpu.py) keep the exact
+fp32 accumulation but carry operands that the 16-bit plans cannot store: every conversion to bf16 / fp16 then
+rounds, ties included, and ``rounding_reference`` restates in float64 where the library rounds and to what.
+
 A helper module, not a conftest: it holds no fixtures and changes nothing about how the suite runs.
 """
 from __future__ import annotations
@@ -484,6 +488,27 @@ class ExactBlock:
         return out if dtype in ("fp32", "fp32_exact") else RNE[dtype](out)
 
 
+def block_expected_rounded(blk: ExactBlock, dtype: str):
+    """(mid, out, largest sum |w||x| + |b|) of a stand-alone DoubleConv on operands that round, in a 16-bit plan
+    T: the host packs RNE_T(fp32(folded weights)) (put_elem), each conv's fp32 accumulator + fp32 bias goes
+    through ReLU and is stored as T (round to nearest even), and unet_block_forward widens the last buffer to
+    fp32.  In float64, with every value a conversion receives asserted to be an fp32 value within fp16's range."""
+    v = torch.from_numpy(blk.x.astype(np.float64))
+    assert np.array_equal(RNE[dtype](blk.x), blk.x)
+    outs, worst = [], 0.0
+    with torch.no_grad():
+        for i in range(2):
+            wf = (blk.w[i].astype(np.float64) * blk.scale[i]).astype(np.float32)
+            w = torch.from_numpy(RNE[dtype](wf).astype(np.float64))
+            b = torch.from_numpy(blk.beta[i].astype(np.float64))
+            worst = max(worst, float(F.conv2d(v.abs(), w.abs(), b.abs(), padding=1).max()))
+            a = F.relu(F.conv2d(v, w, b, padding=1)).numpy()
+            assert np.array_equal(a.astype(np.float32).astype(np.float64), a) and np.abs(a).max() <= F16_MAX
+            outs.append(RNE[dtype](a.astype(np.float32)))
+            v = torch.from_numpy(outs[-1].astype(np.float64))
+    return outs[0], outs[1], worst
+
+
 def quantum(a: np.ndarray) -> float:
     """The largest power of two that divides every (dyadic) element of ``a`` (1.0 for all zeros)."""
     a = np.abs(np.asarray(a, dtype=np.float64))
@@ -544,15 +569,17 @@ def dense_block(name: str, seed: int = 0) -> ExactBlock:
 WIDE_CASES = OrderedDict([("a", (17, 4, 8)), ("b", (4, 17, 8)), ("c", (10, 10, 8)),
                           ("a_lo", (20, 1, 8)), ("b_lo", (1, 20, 8))])
 WIDE_BLOCKS = ("down2", "down4", "conv1")
+WIDE_R12 = (2, 12, 8)     # the 16-bit plans' weight-rounding case "r12": not a three-term case, so not in WIDE_CASES
 WIDE_SIZE = {"down2": (19, 37), "down4": (9, 21), "conv1": (19, 37)}
 
 
 @functools.lru_cache(maxsize=None)
 def wide_block(name: str, case: str, seed: int = 0) -> ExactBlock:
     """First conv: activations below 2^abits, ``nnz`` weights per output channel of magnitude below 2^wbits
-    and random sign at random (cin, tap) positions, integer beta in [-4, 4], scale 1.  Second conv: the
+    and random sign at random (cin, tap) positions, integer beta in [-4, 4], scale 1 (case "r12", for the 16-bit
+    plans: WIDE_R12, weights r12_values x 2^-8 -- see R12_LAYERS -- expected by ``expected_rounded``).  Second conv: the
     centre-tap identity (+1 at (o, o, 1, 1)), beta 0.  nnz * 2^abits * 2^wbits + 4 < 2^24 in every case."""
-    abits, wbits, nnz = WIDE_CASES[case]
+    abits, wbits, nnz = WIDE_R12 if case == "r12" else WIDE_CASES[case]
     cin, cout = BLOCKS[name]
     h, w = WIDE_SIZE[name]
     rng = np.random.default_rng([seed, cin, cout, abits, wbits])
@@ -561,10 +588,11 @@ def wide_block(name: str, case: str, seed: int = 0) -> ExactBlock:
     w0 = np.zeros((cout, k), np.float32)
     for o in range(cout):
         pos = rng.choice(k, nnz, replace=False)
-        w0[o, pos] = rng.integers(1, 2 ** wbits, nnz) * rng.choice([-1.0, 1.0], nnz)
+        mag = r12_values(rng, nnz) if case == "r12" else rng.integers(1, 2 ** wbits, nnz)
+        w0[o, pos] = mag * rng.choice([-1.0, 1.0], nnz)
     ident = np.zeros((cout, cout, 3, 3), np.float32)
     ident[np.arange(cout), np.arange(cout), 1, 1] = 1.0
-    return ExactBlock(name, cin, cout, x, [w0.reshape(cout, cin, 3, 3), ident], [1.0, 1.0],
+    return ExactBlock(name, cin, cout, x, [w0.reshape(cout, cin, 3, 3), ident], [R12_SCALE if case == "r12" else 1.0, 1.0],
                       [rng.integers(-4, 5, cout), np.zeros(cout, np.int64)])
 
 
@@ -585,3 +613,406 @@ def six_and_dropped(blk: ExactBlock):
                 else:
                     dropped = max(dropped, mag)
     return kept.numpy(), used, dropped
+
+
+# ------------------------------------------------------------------------------------------------ section 3
+# Rounding networks: the routing body on operands that the 16-bit plans must ROUND when they store them.
+PLAN_TYPES = {"bf16": ("bf16",) * 6, "fp16": ("fp16",) * 6,
+              "mixed": ("fp16", "fp16", "bf16", "bf16", "bf16", "bf16"),   # csrc/unet_capi.cpp level_dtype
+              "fp32": (None,) * 6, "fp32_exact": (None,) * 6}
+SIG_BITS = {"bf16": 8, "fp16": 11}
+F16_MAX = 65504.0
+# every conversion to a storage type in forward order: (name, level whose type it takes)
+ROUNDING_STORES = [("x", 0), ("c1a", 0), ("c1", 0), ("p1", 1), ("c2a", 1), ("c2", 1), ("p2", 2), ("c3a", 2), ("c3", 2),
+                   ("p3", 3), ("c4a", 3), ("c4", 3), ("p4", 4), ("bna", 4), ("bn", 4), ("u4", 3), ("c5a", 3), ("c5", 3),
+                   ("u3", 2), ("c6a", 2), ("c6", 2), ("u2", 1), ("c7a", 1), ("c7", 1), ("u1", 0), ("c8a", 0), ("head", 0)]
+STORE_LEVEL = dict(ROUNDING_STORES)
+
+
+def round_sig(x: np.ndarray, dtype: str, mode: str = "rne") -> np.ndarray:
+    """float64 -> ``dtype``'s significand width (8 bits bf16, 11 bits fp16) by plain arithmetic, returned as
+    float64.  ``mode``: "rne" (nearest, ties to even), "trunc" (towards zero: a conversion by shift), "away"
+    (nearest, ties away from zero).  For values in both types' normal range (asserted: 2^-14 <= |v| <= 65504 or
+    0), where "rne" is RNE[dtype] (asserted by tests/test_rounding_cpu.py)."""
+    x = np.asarray(x, dtype=np.float64)
+    nz = x != 0
+    assert np.all(np.abs(x[nz]) >= 2.0 ** -14) and np.all(np.abs(x) <= F16_MAX), "outside the shared normal range"
+    _, e = np.frexp(x)                                     # |x| = m 2^e, 0.5 <= m < 1
+    q = np.ldexp(1.0, e - SIG_BITS[dtype])                 # the spacing of dtype's values in [2^(e-1), 2^e)
+    y = x / q
+    r = {"rne": np.rint, "trunc": np.trunc, "away": lambda t: np.sign(t) * np.floor(np.abs(t) + 0.5)}[mode](y)
+    return np.where(nz, r * q, 0.0)
+
+
+def is_tie(x: np.ndarray, dtype: str) -> np.ndarray:
+    """Elementwise: x lies exactly half way between two neighbouring ``dtype`` values."""
+    x = np.abs(np.asarray(x, dtype=np.float64))
+    _, e = np.frexp(x)
+    y = x / np.ldexp(1.0, e - SIG_BITS[dtype])
+    return y - np.floor(y) == 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def _rounding_body(seed: int, c_in: int):
+    """The routing body (_routing_body, its draws untouched) with, from generators of its own: every BatchNorm beta
+    + j / 16, j in [0, 16); every ConvTranspose a second nonzero weight, +-1, per (cout, dy, dx) and an integer
+    bias in [0, 2]."""
+    base, _ = _routing_body(seed, c_in)
+    rng = np.random.default_rng([seed, c_in, 13])
+    sd = dict(base)
+    for name, (_, co) in BLOCKS.items():
+        for idx in (0, 3):
+            beta = base[f"{name}.net.{idx + 1}.bias"].astype(np.float64) + rng.integers(0, 16, co) / 16.0
+            _put_conv_bn(sd, name, idx, exact_fold(base[f"{name}.net.{idx}.weight"], 1.0, beta))
+    for name, ci in (("up4", 1024), ("up3", 512), ("up2", 256), ("up1", 128)):
+        co = ci // 2
+        w = np.array(base[f"{name}.weight"])
+        src = w.argmax(axis=0)                                       # [co, 2, 2]: the +1's input channel
+        other = (src + rng.integers(1, ci, (co, 2, 2))) % ci
+        o, dy, dx = np.meshgrid(np.arange(co), np.arange(2), np.arange(2), indexing="ij")
+        w[other, o, dy, dx] = rng.choice([-1.0, 1.0], (co, 2, 2)).astype(np.float32)
+        assert np.array_equal((w != 0).sum(axis=0), np.full((co, 2, 2), 2))
+        sd[f"{name}.weight"] = w
+        sd[f"{name}.bias"] = rng.integers(0, 3, co).astype(np.float32)
+    for v in sd.values():
+        v.setflags(write=False)
+    return sd
+
+
+def rounding_input(seed: int, n: int, c_in: int, h: int, w: int) -> np.ndarray:
+    """k / 16, k uniform in [0, 2^15), fp32 NCHW: 15 significant bits, below 2048."""
+    rng = np.random.default_rng([seed, n, c_in, h, w, 17])
+    return (rng.integers(0, 2 ** 15, (n, c_in, h, w)) / 16.0).astype(np.float32)
+
+
+def _head_bias(s: np.ndarray, thr) -> np.ndarray:
+    """Per class the integer bias that puts the share of ``s[k] + bias > logit(thr[k])`` nearest one half
+    (asserted within 30 .. 70 %); s = the head's dot products on a probe."""
+    out = np.zeros(len(thr), np.float32)
+    for k, t in enumerate(thr):
+        b = float(np.ceil(logit_cut64(t) - np.median(s[k])))
+        best = min((b + d for d in range(-2, 3)), key=lambda v: abs(float((s[k] + v > logit_cut64(t)).mean()) - 0.5))
+        share = float((s[k] + best > logit_cut64(t)).mean())
+        assert 0.3 <= share <= 0.7, (k, share)
+        out[k] = best
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def rounding_state_dict(seed: int, c_in: int, n_classes: int = 3) -> "OrderedDict[str, np.ndarray]":
+    """A UNet state_dict whose every 16-bit storage point rounds on ``rounding_input``: _rounding_body (+-1 3x3
+    weights, exact in every type, so only activations round; dyadic betas through exact_fold; two-term
+    ConvTranspose with an integer bias) under the dense {-1, 0, +1} head (_dense_head_weights), whose integer
+    biases are chosen, as routing_state_dict does, from the float64 run of a 32 x 32 probe so that each class's
+    logits straddle its cut (the model's default thresholds).  Shared (cached): read-only."""
+    sd = dict(_rounding_body(seed, c_in))
+    w = _dense_head_weights(seed, c_in, n_classes)
+    sd["out_conv.weight"] = w.reshape(n_classes, 64, 1, 1)
+    sd["out_conv.bias"] = np.zeros(n_classes, np.float32)
+    probe = _round_forward(sd, rounding_input(seed, 1, c_in, 32, 32), PLAN_TYPES["fp32"])
+    s = w.astype(np.float64) @ probe["head"][0].reshape(64, -1).astype(np.float64)
+    sd["out_conv.bias"] = _head_bias(s, DEFAULT_THRESHOLDS[:n_classes])
+    out = _ordered(sd, c_in, n_classes)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+# alter = ((store, mode), ...): the reference recomputed with ONE conversion done wrongly -- what the diagnosis
+# compares a wrong tensor with, and the negative controls of tests/test_rounding_cpu.py.  Modes: "trunc", "away"
+# (round_sig); "other": the other 16-bit type; "double": through bf16 first (a 16-bit split-K partial); "none":
+# not rounded at all (an fp32 operand where a 16-bit one is documented); "via_skip" (pooled maps only): the max of
+# the ROUNDED skip instead of the fp32 values.
+ALTER_MODES = ("trunc", "away", "other", "double", "none")
+_WEIGHT_MEMO = {}   # prepared weights of the shared (cached, read-only) state dicts, by array identity
+
+
+# the first store a layer's weights act on (where an altered weight conversion first shows)
+WEIGHT_STORE = {"down4.net.0": "c4a", "down4.net.3": "c4", "conv1.net.3": "head", "up4": "u4", "up1": "u1"}
+
+
+class _Lazy:
+    """A tensor computed when first asked for (a reused prefix of the forward is never computed)."""
+
+    def __init__(self, fn):
+        self.fn, self.v = fn, None
+
+    def get(self):
+        if self.v is None:
+            self.v = self.fn()
+        return self.v
+
+
+def _round_forward(sd, x: np.ndarray, types, alter=(), bound: float = 2.0 ** 20, pre=None,
+                   reuse=None) -> "OrderedDict[str, np.ndarray]":
+    """The forward in float64 with the library's conversions (rounding_reference's docstring lists them);
+    ``types``: the storage type of levels 0..4 (None: fp32, nothing rounds).  Returns every store of
+    ROUNDING_STORES and the logits as fp32 arrays (and into ``pre``, a dict, the fp32 values each conversion
+    received).  ``reuse``: the unaltered result for the same operands and types -- the stores in front of the
+    first altered conversion are taken from it instead of being computed again.  Asserted on the way: every
+    value a conversion receives is exactly an fp32 value, none exceeds fp16's largest finite value, and every
+    accumulation has sum |w||x| + |b| < ``bound`` (2^20 for operands that are multiples of 2^-4: 24 bits)."""
+    alter = dict(alter)
+    o = OrderedDict()
+    order = [n for n, _ in ROUNDING_STORES]
+    first = 0
+    if reuse is not None and alter:
+        first = min(order.index(k) if k in order else order.index(WEIGHT_STORE[k]) if k in WEIGHT_STORE else len(order)
+                    for k in alter)
+
+    def cvt(a: np.ndarray, t, mode="rne"):
+        if t is None or mode == "none":
+            return a
+        if mode in ("rne", "via_skip"):
+            return RNE[t](a.astype(np.float32)).astype(np.float64)
+        if mode == "other":
+            return cvt(a, "fp16" if t == "bf16" else "bf16")
+        if mode == "double":
+            return cvt(cvt(a, "bf16"), t)
+        return round_sig(a, t, mode)
+
+    def store(name: str, lazy: _Lazy) -> _Lazy:
+        if order.index(name) < first:
+            o[name] = reuse[name]
+            return _Lazy(lambda: torch.from_numpy(reuse[name].astype(np.float64)))
+        a = lazy.get().numpy()
+        assert np.array_equal(a.astype(np.float32).astype(np.float64), a), f"{name}: not an fp32 value"
+        assert np.abs(a).max() <= F16_MAX, f"{name}: beyond fp16's range"
+        r = cvt(a, types[STORE_LEVEL[name]], alter.get(name, "rne"))
+        o[name] = r.astype(np.float32)
+        if pre is not None:
+            pre[name] = a.astype(np.float32)
+        return _Lazy(lambda: torch.from_numpy(r))
+
+    def weights(key: str, level: int, fold=None):
+        """RNE_T(fp32(folded weight)) -- unet_capi.cpp put_elem -- and the fp32 bias, both as float64."""
+        t, mode = types[level], alter.get(key, "rne")
+        used = [sd[f"{key}.weight"], sd[f"{key}.bias"]]                    # what the result depends on
+        if fold:
+            used += [sd[f"{fold[0]}.net.{fold[1] + 1}.{f}"] for f in ("weight", "bias", "running_mean", "running_var")]
+        memo = (tuple(id(u) for u in used), t, mode)
+        if memo not in _WEIGHT_MEMO:
+            if fold is None:
+                w, b = sd[f"{key}.weight"].astype(np.float64), sd[f"{key}.bias"].astype(np.float64)
+            else:
+                blk, idx = fold
+                w, b = fold_f64(*(sd[f"{blk}.net.{i}"] for i in (f"{idx}.weight", f"{idx}.bias", f"{idx + 1}.weight",
+                                                                 f"{idx + 1}.bias", f"{idx + 1}.running_mean",
+                                                                 f"{idx + 1}.running_var")))
+            w = w.astype(np.float32).astype(np.float64)
+            b = b.astype(np.float32).astype(np.float64)
+            red = (0,) if key.startswith("up") else (1, 2, 3)
+            wt = torch.from_numpy(cvt(w, t, mode))
+            # (weights, bias, the arrays whose ids are the key -- kept alive, so that no id is ever reused --, the
+            # largest sum |w| of an output, the largest |bias|)
+            _WEIGHT_MEMO[memo] = (wt, torch.from_numpy(b), used, float(wt.abs().sum(dim=red).max()), float(np.abs(b).max()))
+        return _WEIGHT_MEMO[memo]
+
+    def exact(v, wsum, bmax):
+        worst = wsum * float(v.abs().max()) + bmax
+        assert worst < bound, f"accumulation bound: {worst} >= {bound}"
+
+    def conv(v: _Lazy, blk, idx, level) -> _Lazy:
+        def run():
+            w, b, _, wsum, bmax = weights(f"{blk}.net.{idx}", level, (blk, idx))
+            exact(v.get(), wsum, bmax)
+            return F.relu(F.conv2d(v.get(), w, b, padding=1))
+        return _Lazy(run)
+
+    def dc(blk, v, level, mid, out, pooled=None):
+        a = store(mid, conv(v, blk, 0, level))
+        y = conv(a, blk, 3, level)                  # fp32 accumulators + bias, ReLU: what the epilogue holds
+        s = store(out, y)
+        if pooled:                                  # the pooled map: the max of the fp32 values, then ONE conversion
+            src = s if alter.get(pooled) == "via_skip" else y
+            return s, store(pooled, _Lazy(lambda: F.max_pool2d(src.get(), 2)))
+        return s
+
+    def up(key, v, level, out):
+        def run():
+            w, b, _, wsum, bmax = weights(key, level)
+            exact(v.get(), wsum, bmax)
+            return F.conv_transpose2d(v.get(), w, b, stride=2)
+        return store(out, _Lazy(run))
+
+    def cat(u, c):
+        return _Lazy(lambda: torch.cat([u.get(), c.get()], 1))
+
+    with torch.no_grad():
+        t = store("x", _Lazy(lambda: torch.from_numpy(np.asarray(x, dtype=np.float64))))
+        c1, p1 = dc("down1", t, 0, "c1a", "c1", "p1")
+        c2, p2 = dc("down2", p1, 1, "c2a", "c2", "p2")
+        c3, p3 = dc("down3", p2, 2, "c3a", "c3", "p3")
+        c4, p4 = dc("down4", p3, 3, "c4a", "c4", "p4")
+        bn = dc("bottleneck", p4, 4, "bna", "bn")
+        c5 = dc("conv4", cat(up("up4", bn, 4, "u4"), c4), 3, "c5a", "c5")
+        c6 = dc("conv3", cat(up("up3", c5, 3, "u3"), c3), 2, "c6a", "c6")
+        c7 = dc("conv2", cat(up("up2", c6, 2, "u2"), c2), 1, "c7a", "c7")
+        hd = dc("conv1", cat(up("up1", c7, 1, "u1"), c1), 0, "c8a", "head").get()
+        w, b, _, wsum, bmax = weights("out_conv", 0)
+        exact(hd, wsum, bmax)
+        lg = F.conv2d(hd, w, b).numpy()
+    assert np.array_equal(lg.astype(np.float32).astype(np.float64), lg), "logits: not fp32 values"
+    o["logits"] = lg.astype(np.float32)
+    return o
+
+
+# One r12 WEIGHT layer per network (16-bit plans): the weight-side conversions -- the host's put_elem when it packs
+# a layer for its level's type, and for out_conv the head kernel's device-side cast of the fp32 weights to HT.  The
+# layer's nonzero weights of the integer routing network become +-W with W a 12-bit integer in [2048, 4096): bf16
+# keeps 8 of the 12 bits (exact only for multiples of 16, a tie at 8 mod 16), fp16 keeps 11 (every odd W is a tie).
+# A quarter of the weights are forced to 8 mod 16 and a quarter to odd values, the rest drawn uniformly.  Inputs are
+# integers in [0, 3] (routing_input, 2 bits).  The layer's folded weights are W 2^-8, in [8, 16): a power of two
+# changes neither the 12-bit significand nor what a type keeps of it, and the activations behind the layer (up to 40 W
+# unscaled: past fp16's 65504 at conv1.3, up4 and up1) stay in range.  Everything is a multiple of 2^-8 and
+# sum |w||x| + |b| < 2^16 at every layer (asserted by _round_forward): products and sums below 2^24 quanta.
+R12_SCALE = 2.0 ** -8
+R12_LAYERS = WIDE_W_LAYERS + ["out_conv"]
+R12_INPUT_BITS = 2
+R12_MIN_INEXACT, R12_MIN_TIES = 0.25, 0.2     # floors per type, as shares of the layer's nonzero weights
+
+
+def r12_values(rng, count: int) -> np.ndarray:
+    v = rng.integers(2048, 4096, count)
+    i = np.arange(count)
+    v[i % 4 == 0] = (v[i % 4 == 0] & ~15) | 8
+    v[i % 4 == 1] |= 1
+    return v.astype(np.float32)
+
+
+def r12_weight_stats(w: np.ndarray) -> dict:
+    """Per 16-bit type: (share of the nonzero weights the conversion changes, share that are exact ties)."""
+    v = np.abs(np.asarray(w, np.float64)[np.asarray(w) != 0])
+    return {t: (float((round_sig(v, t) != v).mean()), float(is_tie(v, t).mean())) for t in SIG_BITS}
+
+
+@functools.lru_cache(maxsize=None)
+def routing_state_dict_r12(seed: int, c_in: int, layer: str) -> "OrderedDict[str, np.ndarray]":
+    """``routing_state_dict(seed, c_in, 3, "dense")`` (the dense head: all 64 channels reach the logits, and
+    out_conv itself has 64 weights per class to round; its integer biases re-chosen on a 2-bit 32 x 32 probe)
+    with ``layer``'s nonzero weights scaled to r12 values.  The floors R12_MIN_INEXACT and R12_MIN_TIES are
+    asserted for both 16-bit types."""
+    base = routing_state_dict(seed, c_in, 3, "dense")
+    key = f"{layer}.weight"
+    rng = np.random.default_rng([seed, c_in, 12, R12_LAYERS.index(layer)])
+    w = np.array(base[key])
+    nz = w != 0
+    w[nz] = np.sign(w[nz]) * r12_values(rng, int(nz.sum()))
+    out = OrderedDict(base)
+    if ".net." in layer:   # the scale through the BatchNorm fold (gamma = 2^-8): still exact (asserted)
+        blk, _, idx = layer.partition(".net.")
+        ent = exact_fold(w, R12_SCALE, base[f"{blk}.net.{int(idx) + 1}.bias"])
+        w = ent["weight"]
+        ent["g"].setflags(write=False)
+        out[f"{blk}.net.{int(idx) + 1}.weight"] = ent["g"]
+    else:
+        w = w * np.float32(R12_SCALE)
+    for t, (inexact, ties) in r12_weight_stats(w).items():
+        assert inexact >= R12_MIN_INEXACT and ties >= R12_MIN_TIES, (layer, t, inexact, ties)
+    w.setflags(write=False)
+    out[key] = w
+    # the head's integer biases again, from the unrounded float64 run of a 2-bit 32 x 32 probe
+    out["out_conv.bias"] = np.zeros(3, np.float32)
+    probe = _round_forward(out, routing_input(seed, 1, c_in, 32, 32, R12_INPUT_BITS), PLAN_TYPES["fp32"], (),
+                           2.0 ** 24 * R12_SCALE)
+    bias = _head_bias(probe["logits"][0].reshape(3, -1).astype(np.float64), DEFAULT_THRESHOLDS[:3])
+    bias.setflags(write=False)
+    out["out_conv.bias"] = bias
+    return out
+
+
+def _alter_key(alter):
+    return tuple(sorted(dict(alter).items()))
+
+
+@functools.lru_cache(maxsize=None)
+def _rounding_reference(seed, c_in, n, h, w, plan, n_classes, r12, alter):
+    if r12 is None:
+        sd, x = rounding_state_dict(seed, c_in, n_classes), rounding_input(seed, n, c_in, h, w)
+        bound = 2.0 ** 20                              # multiples of 2^-4: 24 bits
+    else:
+        assert n_classes == 3
+        sd, x = routing_state_dict_r12(seed, c_in, r12), routing_input(seed, n, c_in, h, w, R12_INPUT_BITS)
+        bound = 2.0 ** 24 * R12_SCALE                  # multiples of 2^-8
+    types = PLAN_TYPES[plan] if isinstance(plan, str) else tuple(plan)
+    pre = {} if not alter else None                    # kept for the true references only
+    reuse = _rounding_reference(seed, c_in, n, h, w, plan, n_classes, r12, ())[1] if alter else None
+    ref = _round_forward(sd, x, types, alter, bound, pre, reuse)
+    x.setflags(write=False)
+    for v in list(ref.values()) + list((pre or {}).values()):
+        v.setflags(write=False)
+    return x, ref, pre
+
+
+def rounding_reference(seed: int, c_in: int, n: int, h: int, w: int, plan, n_classes: int = 3, r12=None, alter=()):
+    """(x, ref): the input and the forward in float64 with RNE_T applied wherever ``plan`` converts fp32 to a
+    16-bit type T -- the logits and every tensor of FORWARD_ORDER by its ``UNet.intermediate`` name, and the
+    stores nothing can fetch (ROUNDING_STORES), as fp32 arrays.  On ``rounding_state_dict`` and
+    ``rounding_input``; ``r12`` = a layer of R12_LAYERS: on ``routing_state_dict_r12`` and 2-bit integer inputs.
+    ``plan``: a precision plan, or the five levels' types spelt out (the negative controls flip one);
+    ``alter``: see ALTER_MODES.  Cached and shared between tests: read-only.
+
+    T(l) = level_dtype(plan, l) (csrc/unet_capi.cpp): "mixed" is fp16 at levels 0-1 and bf16 at 2-4; the fp32
+    plans convert nothing, so theirs is the unrounded chain.  The conversions, read from csrc/:
+
+      x       the network input -> T(0): x_to_px4_kernel (the fused first conv), first_conv_mfma_kernel's B
+              fragments (unfused)
+      weights every 3x3 and ConvTranspose layer at level l: RNE_T(l)(fp32(folded)) on the host (put_elem); the
+              folded biases stay fp32 and join the fp32 accumulator
+      mid     a DoubleConv's first ReLU output -> T(l): store64_grouped<TO> (the shared epilogue), the fused
+              first conv's LDS tile, splitk_reduce_kernel's store8<TO> under the small-batch plan
+      skip    its second ReLU output -> T(l) likewise (TO)
+      pooled  max over the 2 x 2 window of the fp32 ReLU values -> T(l + 1) (TQ): ONE conversion of the fp32
+              maximum, not a second one of the stored skip (the two differ where T(l) != T(l + 1): p2 of "mixed";
+              here the reference follows the code, which rounds each value it stores once)
+      u_k     ConvTranspose at level l (operands T(l)): fp32 accumulator + fp32 bias -> T(l - 1), the
+              pixel-shuffle store (store64_grouped<TO> in the shared epilogue's EPI_UPSCATTER branch, reached from
+              convT_ring_kernel and from the halo family);
+              with up1 fused into conv2.3 (EPI_UPFUSE) c7 is cast to T(1) in registers (conv_to_xb) exactly as
+              it would have been stored, so u1 has the same bits either way
+      head    conv1.3's ReLU output -> HT = T(0) in registers, and out_conv's fp32 weights -> HT on the device
+              (head_epilogue); the dot accumulates in fp32 and the fp32 bias is added to it: the logits are
+              never rounded
+    Every one is a conversion of an fp32 value by the compiler's (T) cast or the host's f32_to_bf16 / f32_to_f16:
+    round to nearest, ties to even.  Asserted inside: every value converted is exactly an fp32 value (so the
+    result does not depend on accumulation order, split-K or fusion), none exceeds 65504."""
+    return _rounding_reference(seed, c_in, n, h, w, plan if isinstance(plan, str) else tuple(plan), n_classes, r12,
+                               _alter_key(alter))[:2]
+
+
+# shapes of the rounding tests: (seed, c_in, n, h, w).  Seeds of their own generators; the body is the routing body of
+# that seed.  16 x 16 at N = 1: the small-batch plan, 3 and 1 channels.
+ROUNDING_MIN = [(0, 3, 1, 16, 16), (1, 1, 1, 16, 16)]
+ROUNDING_LARGER = [(2, 3, 6, 16, 112), (4, 3, 3, 48, 80)]
+ROUNDING_FORCED = (8, 3, 2, 64, 64)
+ROUNDING_R12 = [(4, 3, 3, 48, 80), (2, 3, 6, 16, 112)]          # N = 3 (small-batch plan) and N = 6
+MIN_CHANGED, MIN_TIES = 0.01, 20                                # per stored tensor at the larger shapes
+
+
+def rounding_coverage(seed, c_in, n, h, w, plan: str, r12=None) -> "OrderedDict[str, tuple]":
+    """Per store of ``plan``'s reference: (elements, elements the conversion changed, exact ties among them),
+    counted on the fp32 values the conversion received."""
+    pre = _rounding_reference(seed, c_in, n, h, w, plan, 3, r12, ())[2]
+    out = OrderedDict()
+    for name, level in ROUNDING_STORES:
+        t = PLAN_TYPES[plan][level]
+        a = pre[name].astype(np.float64)
+        out[name] = (a.size, int((round_sig(a, t) != a).sum()), int(is_tie(a, t).sum()))
+    return out
+
+
+def rounding_fault(name: str, got: np.ndarray, ref_args: tuple, ref_kwargs: dict) -> str:
+    """What a wrong tensor ``name`` (a FORWARD_ORDER name) equals instead: the reference recomputed with the
+    conversion that writes it truncating, rounding half away, converting to the other 16-bit type, rounding
+    twice or (pooled maps) taking the max of the rounded skip -- names the fault, not just the element."""
+    store = "head" if name == "logits" else name
+    modes = ALTER_MODES + (("via_skip",) if name in ("p1", "p2", "p3", "p4") else ())
+    hits = []
+    for mode in modes:
+        alt = rounding_reference(*ref_args, **ref_kwargs, alter=((store, mode),))[1][name]
+        if alt.shape == got.shape and np.array_equal(alt, got):
+            hits.append(mode)
+    names = {"trunc": "truncation", "away": "round-half-away", "other": "the other 16-bit type", "none": "no rounding",
+             "double": "a doubled rounding through bf16", "via_skip": "the max of the rounded skip"}
+    return (f"{name} equals the reference with " + " / ".join(names[m] for m in hits) + f" at store '{store}'") if hits \
+        else f"{name} matches none of the single-fault references (truncation, half-away, other type, double, none)"
