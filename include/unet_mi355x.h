@@ -39,7 +39,8 @@ extern "C" {
                                     three bf16 terms, UNET_DTYPE_F32_EXACT the exact-fp32 MFMA
                                     (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
                                     UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config; then
-                                    unet_head_reserve, unet_head_forward, unet_head_backward) */
+                                    unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
+                                    unet_block_debug_fill) */
 
 /* error codes */
 #define UNET_OK 0
@@ -208,6 +209,18 @@ int unet_forward_timed(unet_handle* h, const void* x, int x_layout, int x_dtype,
  * dst: device buffer receiving fp32 NCHW [N][C][h][w]; *numel receives the element count
  * when dst is NULL. */
 int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel, void* hip_stream);
+
+/* Fill the handle's scratch memory with one byte value (debug / tests of history independence: every output of
+ * every entry point is a function of its arguments and the loaded weights only, never of what an earlier call left
+ * in the scratch, so a call after a fill must give what it gives on a fresh handle; tests/test_history_gpu.py
+ * fills 0xFF, a NaN in every float format).  One hipMemsetAsync over the full allocated size of each scratch
+ * allocation that exists: the forward workspace (unet_reserve), the score, loss and head scratch, and the
+ * preprocess row buffer.  Untouched: weights, the zero page, resize tables, the mask-box sync entries (state with
+ * a defined idle value, not scratch), whatever a unet_graph owns, caller buffers.  Stream-ordered after the
+ * handle's previous call like unet_forward; allocates nothing and leaves captured graphs valid.  A fill between a
+ * forward and its unet_debug_fetch destroys what the fetch reads.  A NULL handle or a byte outside 0..255 is
+ * UNET_EINVAL before any HIP call; with nothing allocated it is UNET_OK. */
+int unet_debug_fill(unet_handle* h, int byte, void* hip_stream);
 
 /* hipGraph of one forward (unet_forward, or unet_forward_boxes when boxes != NULL) over fixed
  * device buffers and a fixed (N, H, W): the 22-launch sequence is captured once and replayed by
@@ -387,6 +400,8 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out);
 int unet_block_load_weights(unet_block* b, const unet_tensor_view* tensors, int n);
 int unet_block_reserve(unet_block* b, int N, int H, int W);
 int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, int W, void* hip_stream);
+/* unet_debug_fill for a block: its workspace (unet_block_reserve), under the same rules. */
+int unet_block_debug_fill(unet_block* b, int byte, void* hip_stream);
 int unet_block_destroy(unet_block* b);
 
 /* Message of the last error on this thread ("" if none). */

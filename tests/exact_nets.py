@@ -1,4 +1,5 @@
-"""Exact-arithmetic operands for the bitwise tests (tests/test_exact_cpu.py, tests/test_exact_gpu.py).
+"""Exact-arithmetic operands for the bitwise tests (tests/test_exact_cpu.py, tests/test_exact_gpu.py; the
+history-independence tests, tests/test_history_*.py, run the same routing check on a handle with a past).
 
 Every generator here builds operands for which every product and every partial sum of a layer is exactly
 representable in fp32 -- and every stored activation in bf16 and fp16 where a 16-bit plan stores it -- so a
@@ -445,8 +446,80 @@ def reference_masks(logits: np.ndarray, thresholds) -> np.ndarray:
     return np.stack([np.stack(list(orc.masks_from_logits(np.array(lg), thresholds).values())) for lg in logits])
 
 
+# The history-independence tests (tests/test_history_cpu.py, tests/test_history_gpu.py): one handle, reserved once at
+# HISTORY_RESERVE (n, h, w), runs HISTORY_STEPS in this order -- the large-batch and the small-batch (split-K) plan
+# alternating, N = 4 | 5 on either side of the small-batch limit, a 1-pixel bottleneck, ragged tiles at every level,
+# W % 32 both ways -- so that every forward's buffers lie over what a forward of another shape left there.
+HISTORY_RESERVE = (6, 64, 128)
+HISTORY_STEPS = [(6, 16, 112), (1, 16, 16), (3, 48, 80), (4, 32, 32), (5, 16, 16), (1, 48, 80), (2, 64, 64)]
+HISTORY_NETS = [(4, 3), (5, 1)]   # (seed, c_in) of the routing networks
+HISTORY_GRAPHS = [(1, 16, 16), (3, 48, 80)]   # captured shapes; HISTORY_STEPS[0] runs eagerly between their replays
+HISTORY_SPLIT = (0, 3, 1, 16, 16)   # the forced two-slice split-K case (ROUTING_SMALL[0])
+HISTORY_FILL = 0xFF   # a NaN in every float format, all-ones mask bits, -1 as an integer
+
+
+def history_block_reserve(name: str):
+    """(n, h, w) a stand-alone block's workspace is reserved at before it runs dense_block(name)."""
+    h, w = BLOCK_SIZE[name]
+    return BLOCK_N + 2, 2 * h + 3, 2 * w + 1
+
+
+def check_routing_model(m, case, dtype: str, tag: str = "", bits: int = 4, wide_w=None, before=None,
+                        every_box_path: bool = False) -> list:
+    """One routing model ``m`` (already holding the case's weights, on its device), one input: logits and every
+    stored intermediate, masks (u8 and packed) and boxes, all bitwise against the oracle.  ``before`` (optional)
+    is called in front of every forward-type call -- never between a forward and the ``UNet.intermediate``
+    fetches that read its workspace.  ``every_box_path``: also forward_boxes with masks=None (the masks then live
+    in the workspace) and masks="bits".  Returns the launch labels of the forward."""
+    import pytest
+    seed, c_in, n, h, w = case
+    before = before or (lambda: None)
+    dev = next(m.parameters()).device
+    x, ref = routing_reference(seed, c_in, n, h, w, bits, wide_w)
+    xd = torch.from_numpy(np.array(x)).to(dev)
+    before()
+    with torch.no_grad():
+        logits = m(xd)
+    torch.cuda.synchronize()
+    labels = m.native_handle(dev).launch_labels_at(n, h, w)
+    # logits and every stored tensor (with up1 fused into conv2.3, EPI_UPFUSE, c7 is never stored)
+    bad = first_stored_mismatch(m, logits.cpu().numpy(), ref, labels)
+    if bad:
+        pytest.fail(f"{dtype} {case} {tag}: {bad}")
+    ref_masks = np.stack([np.stack([orc.masks_from_logits(np.array(ref["logits"][i]))[f] for f in orc.FIELDS])
+                          for i in range(n)])
+    with torch.no_grad():
+        before()
+        masks, lg2 = m.forward_masks(xd, with_logits=True)
+        before()
+        packed = m.forward_masks(xd, packed=True)
+        before()
+        bmasks, boxes = m.forward_boxes(xd, masks="u8")
+    assert np.array_equal(lg2.cpu().numpy(), ref["logits"]), "logits of forward_masks"
+    for name, mk in (("u8", masks.cpu().numpy()), ("boxes' u8", bmasks.cpu().numpy()),
+                     ("packed", np.unpackbits(packed.cpu().numpy(), axis=-1, bitorder="little"))):
+        if not np.array_equal(mk.astype(bool), ref_masks):
+            pytest.fail(f"{dtype} {case} {tag}: " + describe_mismatch(
+                f"{name} masks", mk.astype(bool), ref_masks, labels[21]))
+    assert np.array_equal(boxes.cpu().numpy(), np_boxes(ref_masks)), (boxes.cpu().numpy(), np_boxes(ref_masks))
+    if every_box_path:
+        with torch.no_grad():
+            before()
+            only = m.forward_boxes(xd, masks=None)
+            before()
+            bits_m, bits_b = m.forward_boxes(xd, masks="bits")
+        assert np.array_equal(only.cpu().numpy(), np_boxes(ref_masks)), \
+            ("boxes with the masks in the workspace", only.cpu().numpy(), np_boxes(ref_masks))
+        assert np.array_equal(bits_b.cpu().numpy(), np_boxes(ref_masks)), \
+            ("boxes with packed masks", bits_b.cpu().numpy(), np_boxes(ref_masks))
+        got = np.unpackbits(bits_m.cpu().numpy(), axis=-1, bitorder="little").astype(bool)
+        if not np.array_equal(got, ref_masks):
+            pytest.fail(f"{dtype} {case} {tag}: " + describe_mismatch("boxes' packed masks", got, ref_masks, labels[21]))
+    return labels
+
+
 # ------------------------------------------------------------------------------------------------ section 2
-BLOCK_SIZE = {"down1": (19, 37), "down2": (19, 37), "conv2": (19, 37), "conv1": (19, 37),
+BLOCK_SIZE ={"down1": (19, 37), "down2": (19, 37), "conv2": (19, 37), "conv1": (19, 37),
               "down3": (9, 21), "down4": (9, 21), "conv3": (9, 21), "bottleneck": (5, 7), "conv4": (5, 7)}
 BLOCK_N = 2
 

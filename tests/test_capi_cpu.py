@@ -40,6 +40,11 @@ def test_create_rejects_bad_config_without_gpu():
     assert lib.unet_create(ctypes.byref(bad), ctypes.byref(h)) == native.UNET_EINVAL
     assert b"n_channels" in lib.unet_last_error()
     assert lib.unet_forward(None, None, 0, 0, None, None, 0, 1, 16, 16, None) == native.UNET_EINVAL
+    # the scratch fill: a null handle or block is refused before any HIP call
+    assert lib.unet_debug_fill(None, 0xFF, None) == native.UNET_EINVAL
+    assert b"null" in lib.unet_last_error()
+    assert lib.unet_block_debug_fill(None, 0xFF, None) == native.UNET_EINVAL
+    assert b"null" in lib.unet_last_error()
 
 
 @pytest.mark.parametrize("thr", [0.25, 0.40, 0.30, 0.5, 1e-6, 0.999999])

@@ -12,7 +12,6 @@ import pytest
 import torch
 
 import exact_nets as en
-from oracle import unet_oracle as orc
 from unet_mi355x.model import UNet
 
 pytestmark = pytest.mark.gpu
@@ -28,46 +27,12 @@ def _routing_model(seed, c_in, dtype, wide_w=None):
     return m.to(DEV).eval()
 
 
-def _np_boxes(masks):
-    out = np.full(masks.shape[:2] + (4,), -1, dtype=np.int32)
-    for i in range(masks.shape[0]):
-        for c in range(masks.shape[1]):
-            ys, xs = np.where(masks[i, c])
-            if len(xs):
-                out[i, c] = (xs.min(), ys.min(), xs.max(), ys.max())
-    return out
-
-
 def _check_routing(case, dtype, tag="", bits=4, wide_w=None):
     """One model, one input: logits and every stored intermediate, masks (u8 and packed) and boxes, all
     bitwise against the oracle.  Returns the launch labels of the forward."""
-    seed, c_in, n, h, w = case
-    x, ref = en.routing_reference(seed, c_in, n, h, w, bits, wide_w)
-    m = _routing_model(seed, c_in, dtype, wide_w)
+    m = _routing_model(case[0], case[1], dtype, wide_w)
     try:
-        xd = torch.from_numpy(np.array(x)).to(DEV)
-        with torch.no_grad():
-            logits = m(xd)
-        torch.cuda.synchronize()
-        labels = m.native_handle(torch.device(DEV)).launch_labels_at(n, h, w)
-        # logits and every stored tensor (with up1 fused into conv2.3, EPI_UPFUSE, c7 is never stored)
-        bad = en.first_stored_mismatch(m, logits.cpu().numpy(), ref, labels)
-        if bad:
-            pytest.fail(f"{dtype} {case} {tag}: {bad}")
-        ref_masks = np.stack([np.stack([orc.masks_from_logits(np.array(ref["logits"][i]))[f] for f in orc.FIELDS])
-                              for i in range(n)])
-        with torch.no_grad():
-            masks, lg2 = m.forward_masks(xd, with_logits=True)
-            packed = m.forward_masks(xd, packed=True)
-            bmasks, boxes = m.forward_boxes(xd, masks="u8")
-        assert np.array_equal(lg2.cpu().numpy(), ref["logits"]), "logits of forward_masks"
-        for name, mk in (("u8", masks.cpu().numpy()), ("boxes' u8", bmasks.cpu().numpy()),
-                         ("packed", np.unpackbits(packed.cpu().numpy(), axis=-1, bitorder="little"))):
-            if not np.array_equal(mk.astype(bool), ref_masks):
-                pytest.fail(f"{dtype} {case} {tag}: " + en.describe_mismatch(
-                    f"{name} masks", mk.astype(bool), ref_masks, labels[21]))
-        assert np.array_equal(boxes.cpu().numpy(), _np_boxes(ref_masks)), (boxes.cpu().numpy(), _np_boxes(ref_masks))
-        return labels
+        return en.check_routing_model(m, case, dtype, tag, bits, wide_w)   # the assertions (shared with test_history_gpu)
     finally:
         m.close()
 
@@ -154,8 +119,12 @@ def test_routing_forced_configurations(var, value, tag, dtype, monkeypatch):
         monkeypatch.setenv("UNET_MI355X_FUSE_UP1", "0")
     labels = _check_routing(en.ROUTING_FORCED, dtype, tag)
     _print_labels(f"{dtype} {tag}", labels)
-    # the override took effect: every 3x3 launch (a layer that does not support the configuration falls back
-    # within its family) or every ConvTranspose launch runs the forced kernel family
+    assert_forced_labels(var, value, tag, dtype, labels)
+
+
+def assert_forced_labels(var, value, tag, dtype, labels):
+    """The override took effect: every 3x3 launch (a layer that does not support the configuration falls back
+    within its family) or every ConvTranspose launch runs the forced kernel family."""
     if var == "UNET_MI355X_CFG":
         fam = FAMILY[int(tag[3:])]
         bad = [(i, s) for i, s in enumerate(labels) if i > 0 and i not in UP_LAUNCHES and s and not s.startswith(fam)]

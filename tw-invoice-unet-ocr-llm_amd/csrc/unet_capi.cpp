@@ -1820,6 +1820,33 @@ int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel
   return UNET_OK;
 }
 
+namespace {
+// Every scratch allocation of the handle that exists, over its full allocated size: the forward workspace, the
+// score, loss and head scratch, the preprocess row buffer.  Not the weights, the zero page, the resample tables or
+// the mask-box sync entries (state with a defined idle value), and nothing a unet_graph owns.
+int fill_scratch(unet_handle* h, int byte, void* stream) {
+  const std::pair<void*, size_t> scratch[] = {{h->ws, h->ws_bytes}, {h->score, h->score_bytes},
+                                              {h->loss, h->loss_bytes}, {h->head, h->head_bytes},
+                                              {h->pp_tmp, h->pp_tmp_bytes}};
+  bool any = false;
+  for (const auto& b : scratch) any = any || (b.first && b.second);
+  if (!any) return UNET_OK;
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  order_after_last(h, s);
+  for (const auto& b : scratch)
+    if (b.first && b.second) HIP_TRY(hipMemsetAsync(b.first, byte, b.second, s));
+  mark_done(h, s);
+  return UNET_OK;
+}
+}  // namespace
+
+int unet_debug_fill(unet_handle* h, int byte, void* stream) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (byte < 0 || byte > 255) return fail(UNET_EINVAL, "byte must be 0..255");
+  return fill_scratch(h, byte, stream);
+}
+
 int unet_graph_create(unet_handle* h, const void* x, int x_layout, int x_dtype, void* logits, void* masks,
                       int mask_kind, int32_t* boxes, int N, int H, int W, unet_graph** out) {
   if (!h || !out) return fail(UNET_EINVAL, "null argument");
@@ -2246,6 +2273,12 @@ int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, in
   if (e != hipSuccess) return fail(UNET_EHIP, std::string("block output transpose: ") + hipGetErrorString(e));
   mark_done(&h, s);
   return UNET_OK;
+}
+
+int unet_block_debug_fill(unet_block* b, int byte, void* stream) {
+  if (!b) return fail(UNET_EINVAL, "null block");
+  if (byte < 0 || byte > 255) return fail(UNET_EINVAL, "byte must be 0..255");
+  return fill_scratch(&b->core, byte, stream);
 }
 
 int unet_block_destroy(unet_block* b) {

@@ -132,8 +132,20 @@ class DoubleConv(_Tracked, nn.Module):
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("unet_mi355x.DoubleConv is inference-only (eval BatchNorm folded, no autograd); "
                                "call .eval() or run under torch.no_grad()")
+        blk = self.native_block(x.device)
+        x = x.detach()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.to(torch.float32).contiguous()
+        n, _, h, w = x.shape
+        y = torch.empty((n, self.out_ch, h, w), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            blk.forward(x, y, torch.cuda.current_stream(x.device).cuda_stream)
+        return y
+
+    def native_block(self, device: torch.device) -> native.Block:
+        """The packed native block for ``device`` (re-packs if any parameter changed)."""
         dtype = self.compute_dtype or DEFAULT_DTYPE
-        idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        idx = device.index if device.index is not None else torch.cuda.current_device()
         with self._lock:
             blk = self._blocks.get((idx, dtype))
             if blk is None:
@@ -143,14 +155,18 @@ class DoubleConv(_Tracked, nn.Module):
             if self._packed_sig.get((idx, dtype)) != sig:
                 blk.load_weights(sd)
                 self._packed_sig[(idx, dtype)] = sig
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.to(torch.float32).contiguous()
-        n, _, h, w = x.shape
-        y = torch.empty((n, self.out_ch, h, w), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            blk.forward(x, y, torch.cuda.current_stream(x.device).cuda_stream)
-        return y
+        return blk
+
+    def reserve(self, n: int, h: int, w: int, device=None) -> None:
+        """Pre-allocate the native block's workspace for up to (n, h, w)."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        self.native_block(dev).reserve(n, h, w)
+
+    def debug_fill(self, byte: int, device=None) -> None:
+        """Set the native block's workspace to ``byte`` (unet_block_debug_fill; tests of history independence)."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        with torch.cuda.device(dev):
+            self.native_block(dev).debug_fill(byte, torch.cuda.current_stream(dev).cuda_stream)
 
     def close(self):
         for b in self._blocks.values():
@@ -533,6 +549,13 @@ class UNet(_Tracked, nn.Module):
         with torch.cuda.device(dev):
             h.debug_fetch_into(name, out, stream)
         return out
+
+    def debug_fill(self, byte: int, device=None) -> None:
+        """Set every scratch allocation of the native handle to ``byte`` (unet_debug_fill; tests of history
+        independence).  Not between a forward and ``intermediate``, which reads the workspace."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        with torch.cuda.device(dev):
+            self.native_handle(dev).debug_fill(byte, torch.cuda.current_stream(dev).cuda_stream)
 
     def close(self):
         for h in self._handles.values():

@@ -115,6 +115,7 @@ SIGNATURES = {
     "unet_photo_graph_set_masks": (_i, [_vp, _vp]),
     "unet_forward_timed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.POINTER(ctypes.c_float)]),
     "unet_debug_fetch": (_i, [_vp, ctypes.c_char_p, _vp, ctypes.POINTER(_sz), _vp]),
+    "unet_debug_fill": (_i, [_vp, _i, _vp]),
     "unet_graph_create": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, ctypes.POINTER(_vp)]),
     "unet_graph_launch": (_i, [_vp, _vp]),
     "unet_graph_destroy": (_i, [_vp]),
@@ -127,6 +128,7 @@ SIGNATURES = {
     "unet_block_load_weights": (_i, [_vp, ctypes.POINTER(TensorView), _i]),
     "unet_block_reserve": (_i, [_vp, _i, _i, _i]),
     "unet_block_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "unet_block_debug_fill": (_i, [_vp, _i, _vp]),
     "unet_block_destroy": (_i, [_vp]),
     "unet_last_error": (ctypes.c_char_p, []),
     "unet_abi_version": (_i, []),
@@ -535,6 +537,12 @@ class Handle:
         check(self.lib.unet_debug_fetch(self._h, name.encode(), dst.data_ptr(), ctypes.byref(cnt), stream),
               "unet_debug_fetch")
 
+    def debug_fill(self, byte: int, stream: int) -> None:
+        """unet_debug_fill: every scratch allocation of the handle (workspace, score / loss / head scratch,
+        preprocess row buffer) set to ``byte``, stream-ordered; weights, tables and graphs stay as they are."""
+        with self.lock:
+            check(self.lib.unet_debug_fill(self._h, int(byte), stream), "unet_debug_fill")
+
     def close(self) -> None:
         for gr in list(getattr(self, "_graphs", ())):
             gr.close()
@@ -578,6 +586,16 @@ class Block:
         with self.lock:
             check(self.lib.unet_block_reserve(self._b, n, h, w), "unet_block_reserve")
             check(self.lib.unet_block_forward(self._b, x.data_ptr(), y.data_ptr(), n, h, w, stream), "unet_block_forward")
+
+    def reserve(self, n: int, h: int, w: int) -> None:
+        """unet_block_reserve: size the block's workspace for up to (n, h, w) ahead of the forwards."""
+        with self.lock:
+            check(self.lib.unet_block_reserve(self._b, n, h, w), "unet_block_reserve")
+
+    def debug_fill(self, byte: int, stream: int) -> None:
+        """unet_block_debug_fill: the block's workspace set to ``byte``, stream-ordered."""
+        with self.lock:
+            check(self.lib.unet_block_debug_fill(self._b, int(byte), stream), "unet_block_debug_fill")
 
     def close(self) -> None:
         if getattr(self, "_b", None):
