@@ -443,6 +443,48 @@ def test_head_after_fill(i, head_handle):
         fresh.close()
 
 
+def _tiny_call(what):
+    """(reserve, call) of `what` on tiny operands -- logits [1, 1, 8, 8] with a uint8 target; feat [1, 64, 8, 8] with
+    C = 1 and want_params -- call(handle) -> the outputs' bytes."""
+    gen = torch.Generator(device=DEV).manual_seed(8)
+    if what == "head":
+        feat = torch.randn((1, 64, 8, 8), device=DEV, generator=gen)
+        g = torch.randn((1, 1, 8, 8), device=DEV, generator=gen)
+        w = torch.randn((1, 64), device=DEV, generator=gen)
+        return "head_reserve", lambda h: b"".join(thg.bits(t) for t in h.head_backward(feat, g, w, _stream(),
+                                                                                       want_params=True)[:2])
+    logits = torch.randn((1, 1, 8, 8), device=DEV, generator=gen)
+    target = (torch.rand((1, 8, 8, 1), device=DEV, generator=gen) > 0.5).to(torch.uint8)
+    if what == "score":
+        return "score_reserve", lambda h: thg.bits(h.score(logits, target, _stream())[0])
+    return "loss_reserve", lambda h: b"".join(thg.bits(t) for t in h.loss_grad(logits, target, _stream()))
+
+
+@pytest.mark.parametrize("what", ["score", "loss", "head"])
+def test_too_small_scratch_is_refused_during_capture(what):
+    """A call whose scratch was never reserved, made on a capturing stream, is refused (UNET_ESTATE, naming its
+    unet_<what>_reserve) before any device work; the handle then reserves, runs the same call eagerly and gives
+    bitwise what a second fresh handle gives."""
+    reserve, call = _tiny_call(what)
+    h, fresh = native.Handle(3, 3, "fp32", 0), native.Handle(3, 3, "fp32", 0)
+    try:
+        buf = torch.ones(16, device=DEV)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            buf.zero_()   # the capture is not empty
+            with pytest.raises(RuntimeError, match="capturing stream") as err:
+                call(h)
+        assert f"unet_{what}_reserve" in str(err.value)
+        del graph
+        getattr(h, reserve)(1, 8, 8)
+        got, want = call(h), call(fresh)   # the fresh handle grows its scratch in the call: no capture, no refusal
+        assert len(got) > 0 and got == want
+    finally:
+        h.close()
+        fresh.close()
+
+
 # ------------------------------------------------------------------------------------ f. preprocess row buffer
 def test_preprocess_after_fill():
     """A 1400 x 1100 photo sizes the row buffer of the two-pass resize; then, with the buffer filled in front of every

@@ -35,12 +35,15 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return fail(UNET_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+// UNET_OK, or on a HIP error `code` with "<what>: <the error's text>"
+int hip_ok(hipError_t e, const char* what, int code = UNET_EHIP) {
+  return e == hipSuccess ? UNET_OK : fail(code, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIP_CHECK(expr, what)                        \
+  do {                                               \
+    if (int rc_ = hip_ok((expr), what)) return rc_;  \
   } while (0)
+#define HIP_TRY(expr) HIP_CHECK(expr, #expr)
 
 struct DeviceGuard {
   int prev = -1;
@@ -97,6 +100,12 @@ struct Buffers {
   size_t tA, cat1, cat2, cat3, cat4, p1, p2, p3, p4, bnb, tB, mbits, xpx, part, total;  // byte offsets
 };
 
+// A grow-only device buffer of a handle whose content no call expects to find again (grow, kScratch).
+struct Scratch {
+  char* p = nullptr;
+  size_t bytes = 0;
+};
+
 }  // namespace
 
 struct unet_handle {
@@ -122,14 +131,12 @@ struct unet_handle {
   float* head_b = nullptr;
   void* zero = nullptr;
   bool loaded = false;
-  char* ws = nullptr;
-  size_t ws_bytes = 0;
+  Scratch ws;           // the forward's activation workspace (plan)
   int lastN = 0, lastH = 0, lastW = 0;
   std::vector<void*> allocs;
   // (ih, iw, oh, ow) -> tables, most recently used first
   std::list<std::pair<std::tuple<int, int, int, int>, ResampleStore>> resample;
-  uint8_t* pp_tmp = nullptr;              // horizontal-pass rows of unet_preprocess
-  size_t pp_tmp_bytes = 0;
+  Scratch pp_tmp;                         // horizontal-pass rows of unet_preprocess
   std::string labels[UNET_NUM_LAUNCHES];   // kernel instantiation of every launch
   float thr_logit[kMaxClasses];           // per-class logit cut, see unet_logit_cut
   // stream ordering of the shared workspace: the last call's completion event and stream
@@ -154,16 +161,13 @@ struct unet_handle {
   int box_sync_n = 0;
   // unet_score's partial slabs: its own allocation (the forward workspace and its size are untouched), grown by
   // unet_score_reserve / unet_score
-  void* score = nullptr;
-  size_t score_bytes = 0;
+  Scratch score;
   // unet_loss_grad's scratch (the score's slabs of its own step 1, the entries, the gradient coefficients): its own
   // allocation too, grown by unet_loss_reserve / unet_loss_grad
-  void* loss = nullptr;
-  size_t loss_bytes = 0;
+  Scratch loss;
   // unet_head_backward's slabs (fp64 partials of grad_w / grad_b): its own allocation too, grown by
   // unet_head_reserve / unet_head_backward
-  void* head = nullptr;
-  size_t head_bytes = 0;
+  Scratch head;
 };
 
 struct unet_graph {
@@ -451,8 +455,7 @@ Buffers plan(const unet_handle* h, int N, int H, int W) {
 }
 
 int dev_alloc(unet_handle* h, void** p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) return fail(UNET_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  if (int rc = hip_ok(hipMalloc(p, bytes), "hipMalloc", UNET_ENOMEM)) return rc;
   h->allocs.push_back(*p);
   return UNET_OK;
 }
@@ -620,6 +623,18 @@ int pack3x3(unet_handle* h, Layer& L, const std::vector<double>& w, const std::v
   if (!rc) rc = upload(h, (void**)&L.b, bf.data(), bf.size() * 4);
   return rc;
 }
+// The first conv (C -> 64) from its folded weights: fp32 w0 and b0, and on a 16-bit operand type t0 the MFMA
+// operand w0p (pack_first_mfma).
+int upload_first_conv(unet_handle* h, DType t0, int C, const std::vector<double>& w, const std::vector<double>& b) {
+  const std::vector<float> wf(w.begin(), w.end()), bf(b.begin(), b.end());
+  h->w0p = nullptr;
+  int rc = upload(h, (void**)&h->w0, wf.data(), wf.size() * 4);
+  if (!rc) rc = upload(h, (void**)&h->b0, bf.data(), bf.size() * 4);
+  if (rc || t0 == DType::F32) return rc;
+  std::vector<uint8_t> pk;
+  pack_first_mfma(t0, w, C, pk);
+  return upload(h, &h->w0p, pk.data(), pk.size());
+}
 
 // conv2.3 + up1 (EPI_UPFUSE): conv2.3's ring stream (one 128-row tile, S = 9 * cin / BKE steps,
 // as pack3x3) followed by 8 ConvTranspose steps u = (quadrant u >> 1, K blocks 2 (u & 1) + kbl):
@@ -711,6 +726,39 @@ void mark_done(unet_handle* h, hipStream_t s) {
     h->pending = true;
   }
 }
+// One launch on the handle's device, ordered after the previous call and marked as the last: launch(s) returns the
+// hipError_t, a failure is reported as "<what>: <the error's text>".
+template <typename F>
+int launch_on(unet_handle* h, void* stream, const char* what, F launch) {
+  DeviceGuard g(h->cfg.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  order_after_last(h, s);
+  HIP_CHECK(launch(s), what);
+  mark_done(h, s);
+  return UNET_OK;
+}
+// A graph of the handle's work: body(cs) runs under a thread-local capture of a new non-blocking stream cs, after
+// prepare(cs) outside the capture (both return a UNET_* code), and the result is instantiated into gr.  The capture
+// is ended whatever body returns; on a failure the caller releases what gr owns.  stream_what: the message of a
+// failed stream creation (the two kinds of graph have always reported it differently).
+template <typename P, typename F>
+int capture(unet_handle* h, unet_graph* gr, const char* stream_what, P prepare, F body) {
+  hipStream_t cs = nullptr;
+  HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), stream_what);
+  int rc = prepare(cs);
+  if (!rc) rc = hip_ok(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture");
+  if (!rc) {
+    h->capturing = true;
+    rc = body(cs);
+    h->capturing = false;
+    const hipError_t e = hipStreamEndCapture(cs, &gr->graph);
+    if (!rc) rc = hip_ok(e, "hipStreamEndCapture");
+    if (!rc) rc = hip_ok(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0), "hipGraphInstantiate");
+  }
+  (void)hipStreamDestroy(cs);
+  if (!rc) gr->generation = h->generation;
+  return rc;
+}
 
 // Every device buffer that queued work may still read is freed only after that work.
 void drain(unet_handle* h) {
@@ -723,30 +771,55 @@ void free_resample(ResampleStore& st) {
   st.bufs.clear();
 }
 
+// Every scratch buffer of the handle: free_all frees and fill_scratch poisons what is listed here.
+Scratch unet_handle::*const kScratch[] = {&unet_handle::ws, &unet_handle::score, &unet_handle::loss, &unet_handle::head,
+                                          &unet_handle::pp_tmp};
+
 void free_all(unet_handle* h) {
   drain(h);
   for (void* p : h->allocs) (void)hipFree(p);
   h->allocs.clear();
   for (auto& kv : h->resample) free_resample(kv.second);
   h->resample.clear();
-  if (h->pp_tmp) (void)hipFree(h->pp_tmp);
-  h->pp_tmp = nullptr;
-  h->pp_tmp_bytes = 0;
-  if (h->ws) (void)hipFree(h->ws);
-  h->ws = nullptr;
-  h->ws_bytes = 0;
+  for (auto m : kScratch) {
+    if ((h->*m).p) (void)hipFree((h->*m).p);
+    h->*m = Scratch{};
+  }
   if (h->box_sync) (void)hipFree(h->box_sync);
   h->box_sync = nullptr;
   h->box_sync_n = 0;
-  if (h->score) (void)hipFree(h->score);
-  h->score = nullptr;
-  h->score_bytes = 0;
-  if (h->loss) (void)hipFree(h->loss);
-  h->loss = nullptr;
-  h->loss_bytes = 0;
-  if (h->head) (void)hipFree(h->head);
-  h->head = nullptr;
-  h->head_bytes = 0;
+}
+
+// sc grown to at least `need` bytes; a failure reports "<what><call>: <the error's text>" (call: empty for the
+// preprocess buffer, whose message never named the allocation).
+int grow(unet_handle* h, Scratch& sc, size_t need, const char* what, const char* call = " hipMalloc") {
+  if (need <= sc.bytes) return UNET_OK;
+  if (sc.p) {
+    drain(h);   // queued work may still use the old buffer
+    (void)hipFree(sc.p);
+    sc = Scratch{};
+  }
+  const hipError_t e = hipMalloc((void**)&sc.p, need);
+  if (e != hipSuccess) sc.p = nullptr;
+  else sc.bytes = need;
+  return hip_ok(e, (std::string(what) + call).c_str(), UNET_ENOMEM);
+}
+// The workspace alone has pointers that graphs capture (they go stale: generation, bumped whenever it grows, the
+// first time included) and a caller that has not set the device (unet_block_reserve).
+int grow_workspace(unet_handle* h, size_t need, const char* what) {
+  if (need <= h->ws.bytes) return UNET_OK;
+  DeviceGuard g(h->cfg.device);
+  ++h->generation;
+  return grow(h, h->ws, need, what);
+}
+// The call-time check of a scratch that only its unet_<what>_reserve may grow under capture.
+int ensure_scratch(unet_handle* h, Scratch& sc, size_t need, void* stream, const char* name) {
+  if (need <= sc.bytes) return UNET_OK;
+  const std::string what(name);
+  DeviceGuard g(h->cfg.device);
+  if (stream_capturing(h, static_cast<hipStream_t>(stream)))
+    return fail(UNET_ESTATE, what + " scratch too small on a capturing stream: call unet_" + what + "_reserve first");
+  return grow(h, sc, need, (what + " scratch").c_str());
 }
 
 // At least n idle mask-box sync entries (at least 1024: N * n_classes up to 1024 never reallocates).
@@ -764,13 +837,10 @@ int ensure_box_sync(unet_handle* h, int n) {
   if (h->box_sync) (void)hipFree(h->box_sync);
   h->box_sync = nullptr;
   h->box_sync_n = 0;
-  hipError_t e = hipMalloc((void**)&h->box_sync, idle.size() * sizeof(int));
-  if (e != hipSuccess) {
-    h->box_sync = nullptr;
-    return fail(UNET_ENOMEM, std::string("mask-box sync hipMalloc: ") + hipGetErrorString(e));
-  }
-  e = hipMemcpy(h->box_sync, idle.data(), idle.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("mask-box sync init: ") + hipGetErrorString(e));
+  const hipError_t e = hipMalloc((void**)&h->box_sync, idle.size() * sizeof(int));
+  if (e != hipSuccess) h->box_sync = nullptr;
+  if (int rc = hip_ok(e, "mask-box sync hipMalloc", UNET_ENOMEM)) return rc;
+  HIP_CHECK(hipMemcpy(h->box_sync, idle.data(), idle.size() * sizeof(int), hipMemcpyHostToDevice), "mask-box sync init");
   h->box_sync_n = n;
   return UNET_OK;
 }
@@ -778,8 +848,7 @@ int ensure_box_sync(unet_handle* h, int n) {
 // The plumbing unet_* and unet_block_* share.  A new handle's completion event and zero page (the caller has set
 // the device and deletes the handle on failure):
 int init_handle(unet_handle* h) {
-  hipError_t e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+  HIP_CHECK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming), "hipEventCreate");
   std::vector<uint8_t> z(4096, 0);   // zero page: conv padding source, + 64 B per K chunk (ring halo cursors)
   const int rc = upload(h, &h->zero, z.data(), z.size());
   if (rc) { free_all(h); (void)hipEventDestroy(h->done); }
@@ -793,25 +862,6 @@ void reset_weights(unet_handle* h) {
     if (p != h->zero) (void)hipFree(p);
   h->allocs.assign(1, h->zero);
   h->loaded = false;
-}
-// a workspace of at least `need` bytes
-int grow_workspace(unet_handle* h, size_t need, const char* what) {
-  if (need <= h->ws_bytes) return UNET_OK;
-  DeviceGuard g(h->cfg.device);
-  ++h->generation;
-  if (h->ws) {
-    drain(h);   // the old workspace may still be in use by queued forwards
-    (void)hipFree(h->ws);
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-  }
-  hipError_t e = hipMalloc((void**)&h->ws, need);
-  if (e != hipSuccess) {
-    h->ws = nullptr;
-    return fail(UNET_ENOMEM, std::string(what) + " hipMalloc: " + hipGetErrorString(e));
-  }
-  h->ws_bytes = need;
-  return UNET_OK;
 }
 // The three-term fp32 plan (unet_handle::f32x3) of a dtype: 2 = the split-once 128-row tiles on the Cout >= 128
 // layers (x3 = 3), 64-row tiles splitting per tap elsewhere (x3 = 2); 1 = x3 = 2 everywhere; 0 = exact fp32
@@ -892,16 +942,14 @@ int build_resample(int ih, int iw, int oh, int ow, ResampleStore& st) {
   for (int i = 0; i < 4; ++i) {
     void* d = nullptr;
     const size_t bytes = src[i]->size() * sizeof(int);
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e != hipSuccess) {
-      free_resample(st);
-      return fail(UNET_ENOMEM, std::string("resample tables: ") + hipGetErrorString(e));
+    int rc = hip_ok(hipMalloc(&d, bytes), "resample tables", UNET_ENOMEM);
+    if (!rc) {
+      st.bufs.push_back(d);
+      rc = hip_ok(hipMemcpy(d, src[i]->data(), bytes, hipMemcpyHostToDevice), "resample tables upload");
     }
-    st.bufs.push_back(d);
-    e = hipMemcpy(d, src[i]->data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
+    if (rc) {
       free_resample(st);
-      return fail(UNET_EHIP, std::string("resample tables upload: ") + hipGetErrorString(e));
+      return rc;
     }
     *dst[i] = static_cast<const int*>(d);
   }
@@ -916,6 +964,37 @@ int check_geometry(const unet_handle* h, int N, int H, int W) {
   if ((long long)N * H * W > (1LL << 31) / 2) return fail(UNET_ESHAPE, "N*H*W too large for one call");
   (void)h;
   return UNET_OK;
+}
+
+// the precision plan and the device ordinal of a unet_create / unet_block_create configuration (the block checks
+// its shapes, which depend on the plan, between the two)
+int check_dtype(int dtype) {
+  return dtype >= 0 && dtype <= UNET_DTYPE_F32_EXACT ? UNET_OK : fail(UNET_EINVAL, "bad dtype");
+}
+int check_device(int device) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(UNET_EINVAL, "bad device ordinal");
+  return UNET_OK;
+}
+
+// The argument checks unet_score, unet_loss_grad and unet_head_* share.  plane_geometry: N, H, W positive and
+// N x `units` (an image's spans or tiles) within 31 bits; word: the call in the message
+int check_positive(int N, int H, int W) {
+  return N > 0 && H > 0 && W > 0 ? UNET_OK : fail(UNET_EINVAL, "N, H and W must be positive");
+}
+int check_units(int N, long long units, const char* word) {
+  return N * units <= 0x7FFFFFFFLL ? UNET_OK : fail(UNET_EINVAL, std::string("N x H x W too large for one ") + word);
+}
+int plane_geometry(int N, int H, int W, long long units, const char* word) {
+  const int rc = check_positive(N, H, W);
+  return rc ? rc : check_units(N, units, word);
+}
+int check_classes(int C) { return C >= 1 && C <= kMaxClasses ? UNET_OK : fail(UNET_EINVAL, "C must be 1..4"); }
+int check_target_kind(int kind) {
+  return kind == UNET_TGT_F32_NCHW || kind == UNET_TGT_U8_NHWC
+             ? UNET_OK
+             : fail(UNET_EINVAL, "target_kind must be UNET_TGT_F32_NCHW or UNET_TGT_U8_NHWC");
 }
 
 const char* tname(DType t) { return t == DType::F32 ? "float" : t == DType::BF16 ? "__bf16" : "_Float16"; }
@@ -1082,10 +1161,9 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   if (!cfg || !out) return fail(UNET_EINVAL, "null argument");
   if (cfg->n_channels != 1 && cfg->n_channels != 3) return fail(UNET_EINVAL, "n_channels must be 1 or 3");
   if (cfg->n_classes < 1 || cfg->n_classes > kMaxClasses) return fail(UNET_EINVAL, "n_classes must be 1..4");
-  if (cfg->dtype < 0 || cfg->dtype > UNET_DTYPE_F32_EXACT) return fail(UNET_EINVAL, "bad dtype");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(UNET_EINVAL, "bad device ordinal");
+  int rc = check_dtype(cfg->dtype);
+  if (!rc) rc = check_device(cfg->device);
+  if (rc) return rc;
   unet_handle* h = new unet_handle();
   h->cfg = *cfg;
   const bool f32 = cfg->dtype == UNET_DTYPE_F32 || cfg->dtype == UNET_DTYPE_F32_EXACT;
@@ -1174,7 +1252,7 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   });
   build_labels(h);   // after every layer's configuration (3x3 and ConvTranspose) is final
   DeviceGuard g(cfg->device);
-  const int rc = init_handle(h);
+  rc = init_handle(h);
   if (rc) { delete h; return rc; }
   *out = h;
   return UNET_OK;
@@ -1201,19 +1279,11 @@ int unet_load_weights(unet_handle* h, const unet_tensor_view* t, int n) {
   if (!rc) rc = check_f16_range(h->L[D1B].dt, w, b, "down1.net.0");
   if (rc) return rc;
   {
-    std::vector<float> wf(w.begin(), w.end()), bf(b.begin(), b.end());
-    rc = upload(h, (void**)&h->w0, wf.data(), wf.size() * 4);
-    if (!rc) rc = upload(h, (void**)&h->b0, bf.data(), bf.size() * 4);
-    if (rc) return rc;
-    h->w0p = nullptr;
-    h->w0r = nullptr;
     const DType t0 = h->L[D1B].dt;
-    if (t0 != DType::F32) {   // MFMA operand [t][m][16 rows][16 k] (first_conv_mfma_kernel), packed row
-      // rho = 16t + r = natural channel natural_of_packed(rho), k = 4q + c <-> tap first_tap(4m + q) (< 9), channel c (< C)
-      std::vector<uint8_t> pk;
-      pack_first_mfma(t0, w, C, pk);
-      rc = upload(h, &h->w0p, pk.data(), pk.size());
-      if (rc) return rc;
+    h->w0r = nullptr;
+    rc = upload_first_conv(h, t0, C, w, b);
+    if (rc) return rc;
+    if (t0 != DType::F32) {
       // the ring kernel's fused first conv: [cb][t][m][16 rows][16 k], row (cb, t, r) = channel
       // 32cb + 8(r>>2) + 4t + (r&3), k = 4q + c <-> tap first_tap(4m + q) (15 = zero), channel c (< C)
       std::vector<uint8_t> pr((size_t)2 * 2 * 3 * 16 * 16 * 2, 0);
@@ -1367,12 +1437,9 @@ int run_igemm(unet_handle* h, int id, const Layer& L, int epi, const void* in, i
     }
     hipError_t e = launch_igemm(L.dt, L.dt, L.dt, L.cfg, L.taps, EPI_PARTIAL, a, s);
     if (e == hipSuccess) e = launch_splitk_reduce(L.dto, epi == EPI_POOL ? L.dtq : L.dto, epi, a, s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("split-K igemm launch: ") + hipGetErrorString(e));
-    return UNET_OK;
+    return hip_ok(e, "split-K igemm launch");
   }
-  hipError_t e = launch_igemm(L.dt, L.dto, epi == EPI_POOL ? L.dtq : L.dto, cfg, L.taps, epi, a, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("igemm launch: ") + hipGetErrorString(e));
-  return UNET_OK;
+  return hip_ok(launch_igemm(L.dt, L.dto, epi == EPI_POOL ? L.dtq : L.dto, cfg, L.taps, epi, a, s), "igemm launch");
 }
 
 // The launch sequence of UNet.forward (unet_model.py:55-86).  ev (optional, kLaunches+1
@@ -1391,7 +1458,7 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
   int rc = check_geometry(h, N, H, W);
   if (rc) return rc;
   // no allocation (and so no hidden device synchronisation) here: unet_reserve sizes the workspace
-  if (plan(h, N, H, W).total > h->ws_bytes)
+  if (plan(h, N, H, W).total > h->ws.bytes)
     return fail(UNET_ESTATE, "workspace too small for this (N, H, W): call unet_reserve first");
   if (boxes && N * h->cfg.n_classes > h->box_sync_n)
     return fail(UNET_ESTATE, "mask-box sync entries too few for this N: call unet_reserve first");
@@ -1399,7 +1466,7 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
   hipStream_t s = static_cast<hipStream_t>(stream);
   order_after_last(h, s);
   const Buffers B = plan(h, N, H, W);
-  char* ws = h->ws;
+  char* ws = h->ws.p;
   auto buf = [&](size_t off) { return static_cast<void*>(ws + off); };
   if (boxes && (!masks || mask_kind == UNET_MASK_NONE)) {   // boxes only: bit masks into the workspace
     masks = buf(B.mbits);
@@ -1416,14 +1483,13 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
   const void* x0 = x;
   if (x_px4 && !cfg_fused_in(h->L[D1B].cfg)) return fail(UNET_EINVAL, "pre-cast input on a plan without the fused first conv");
   if (cfg_fused_in(h->L[D1B].cfg) && !x_px4) {
-    hipError_t e = launch_x_to_px4(h->L[D1B].dt, x, x_layout, x_dtype, N, C, H, W, buf(B.xpx), s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("input pre-cast launch: ") + hipGetErrorString(e));
+    HIP_CHECK(launch_x_to_px4(h->L[D1B].dt, x, x_layout, x_dtype, N, C, H, W, buf(B.xpx), s), "input pre-cast launch");
     x0 = buf(B.xpx);
   } else if (!x_px4) {
     const float* xf = static_cast<const float*>(x);
     if (x_layout != UNET_LAYOUT_NCHW || x_dtype != UNET_IN_F32) {
-      hipError_t e = launch_x_to_nchw_f32(x, x_layout, x_dtype, N, C, H, W, static_cast<float*>(buf(B.xpx)), s);
-      if (e != hipSuccess) return fail(UNET_EHIP, std::string("input conversion launch: ") + hipGetErrorString(e));
+      HIP_CHECK(launch_x_to_nchw_f32(x, x_layout, x_dtype, N, C, H, W, static_cast<float*>(buf(B.xpx)), s),
+                "input conversion launch");
       xf = static_cast<const float*>(buf(B.xpx));
     }
     FirstConvArgs f{};
@@ -1433,8 +1499,7 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
     f.b = h->b0;
     f.out = buf(B.tA);
     f.N = N; f.C = C; f.H = H; f.W = W;
-    hipError_t e = launch_first_conv(h->L[D1B].dt, f, s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("first conv launch: ") + hipGetErrorString(e));
+    HIP_CHECK(launch_first_conv(h->L[D1B].dt, f, s), "first conv launch");
   }
 
   auto at = [&](size_t Buffers::*m) { return m ? buf(B.*m) : nullptr; };
@@ -1450,9 +1515,9 @@ int forward_impl(unet_handle* h, const void* x, int x_layout, int x_dtype, void*
     if (rc) return rc;
   }
   if (boxes) {   // per-(image, field) mask bounding boxes (inference.py:84-90)
-    hipError_t e = launch_mask_boxes(static_cast<const uint8_t*>(masks), mask_kind, N, h->cfg.n_classes, H, W,
-                                     boxes, h->box_sync, s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("mask boxes launch: ") + hipGetErrorString(e));
+    HIP_CHECK(launch_mask_boxes(static_cast<const uint8_t*>(masks), mask_kind, N, h->cfg.n_classes, H, W, boxes,
+                                h->box_sync, s),
+              "mask boxes launch");
   }
   mark();
   mark_done(h, s);
@@ -1481,7 +1546,6 @@ int unet_preprocess(unet_handle* h, const void* img, int ih, int iw, int channel
   if (ih <= 0 || iw <= 0 || oh <= 0 || ow <= 0 || (long long)ih * iw > (1LL << 30) || oh > 16384 || ow > 16384)
     return fail(UNET_EINVAL, "bad image or output size");
   DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const auto key = std::make_tuple(ih, iw, oh, ow);
   auto it = h->resample.begin();
   while (it != h->resample.end() && it->first != key) ++it;
@@ -1501,22 +1565,10 @@ int unet_preprocess(unet_handle* h, const void* img, int ih, int iw, int channel
   }
   const ResamplePlan& p = it->second.plan;
   const size_t tmp = p.need_h ? (size_t)p.h_rows * ow * channels : 0;
-  if (tmp > h->pp_tmp_bytes) {
-    if (h->pp_tmp) {
-      drain(h);
-      (void)hipFree(h->pp_tmp);
-      h->pp_tmp = nullptr;
-      h->pp_tmp_bytes = 0;
-    }
-    hipError_t e = hipMalloc((void**)&h->pp_tmp, tmp);
-    if (e != hipSuccess) return fail(UNET_ENOMEM, std::string("preprocess buffer: ") + hipGetErrorString(e));
-    h->pp_tmp_bytes = tmp;
-  }
-  order_after_last(h, s);
-  hipError_t e = launch_resample(p, static_cast<const uint8_t*>(img), channels, h->pp_tmp, x, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("resample launch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  if (int rc = grow(h, h->pp_tmp, tmp, "preprocess buffer", "")) return rc;   // also on a capturing stream
+  return launch_on(h, stream, "resample launch", [&](hipStream_t s) {
+    return launch_resample(p, static_cast<const uint8_t*>(img), channels, reinterpret_cast<uint8_t*>(h->pp_tmp.p), x, s);
+  });
 }
 
 int unet_crop_stats(const void* img, int ih, int iw, int channels, const int32_t* boxes, int n_boxes, int box_h,
@@ -1527,38 +1579,22 @@ int unet_crop_stats(const void* img, int ih, int iw, int channels, const int32_t
   if (ih <= 0 || iw <= 0 || (long long)ih * iw > (1LL << 30) || box_h <= 0 || box_w <= 0 || n_boxes <= 0 ||
       n_boxes > 65535 || !(pad >= 0.0 && pad < 1.0))
     return fail(UNET_EINVAL, "bad image size, box geometry, box count or pad");
-  hipError_t e = launch_crop_stats(static_cast<const uint8_t*>(img), ih, iw, channels, boxes, n_boxes, box_h, box_w,
-                                   pad, rects, reinterpret_cast<unsigned long long*>(sums), nullptr,
-                                   static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("crop stats launch: ") + hipGetErrorString(e));
-  return UNET_OK;
+  return hip_ok(launch_crop_stats(static_cast<const uint8_t*>(img), ih, iw, channels, boxes, n_boxes, box_h, box_w, pad,
+                                  rects, reinterpret_cast<unsigned long long*>(sums), nullptr,
+                                  static_cast<hipStream_t>(stream)),
+                "crop stats launch");
 }
 
 namespace {
 int score_geometry(int N, int H, int W, int K) {
-  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
+  if (int rc = check_positive(N, H, W)) return rc;
   if (K < 0 || K > kScoreMaxK) return fail(UNET_EINVAL, "K (sweep candidates) must be 0..64");
-  if ((long long)N * kMaxClasses * score_spans((long long)H * W) > 0x7FFFFFFFLL)
-    return fail(UNET_EINVAL, "N x H x W too large for one score");
-  return UNET_OK;
+  return check_units(N, kMaxClasses * score_spans((long long)H * W), "score");
 }
-// a score scratch of at least `need` bytes
-int grow_score(unet_handle* h, size_t need) {
-  if (need <= h->score_bytes) return UNET_OK;
-  if (h->score) {
-    drain(h);   // queued scores may still read the old slabs
-    (void)hipFree(h->score);
-    h->score = nullptr;
-    h->score_bytes = 0;
-  }
-  hipError_t e = hipMalloc(&h->score, need);
-  if (e != hipSuccess) {
-    h->score = nullptr;
-    return fail(UNET_ENOMEM, std::string("score scratch hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->score_bytes = need;
-  return UNET_OK;
+int loss_geometry(int N, int H, int W) {
+  return plane_geometry(N, H, W, kMaxClasses * score_spans((long long)H * W), "loss");
 }
+int head_geometry(int N, int H, int W) { return plane_geometry(N, H, W, head_tiles((long long)H * W), "head call"); }
 }  // namespace
 
 int unet_score_reserve(unet_handle* h, int N, int H, int W, int K) {
@@ -1566,7 +1602,7 @@ int unet_score_reserve(unet_handle* h, int N, int H, int W, int K) {
   const int rc = score_geometry(N, H, W, K);
   if (rc) return rc;
   DeviceGuard g(h->cfg.device);
-  return grow_score(h, score_scratch_bytes((long long)N * kMaxClasses, (long long)H * W, K));
+  return grow(h, h->score, score_scratch_bytes((long long)N * kMaxClasses, (long long)H * W, K), "score scratch");
 }
 
 int unet_score(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
@@ -1575,13 +1611,13 @@ int unet_score(unet_handle* h, const float* logits, const void* target, int targ
   // every argument check comes before the first HIP call (and before the handle is read)
   if (!h) return fail(UNET_EINVAL, "null handle");
   if (!logits || !target || !entries) return fail(UNET_EINVAL, "logits, target and entries must not be NULL");
-  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
-  if (target_kind != UNET_TGT_F32_NCHW && target_kind != UNET_TGT_U8_NHWC)
-    return fail(UNET_EINVAL, "target_kind must be UNET_TGT_F32_NCHW or UNET_TGT_U8_NHWC");
+  int rc = check_classes(C);
+  if (!rc) rc = check_target_kind(target_kind);
+  if (rc) return rc;
   if (hist && !sweep_probs) return fail(UNET_EINVAL, "hist given without sweep_probs");
   if (sweep_probs && !hist) return fail(UNET_EINVAL, "sweep_probs given without hist");
   if (!sweep_probs) K = 0;
-  int rc = score_geometry(N, H, W, K);
+  rc = score_geometry(N, H, W, K);
   if (rc) return rc;
   if (sweep_probs && K < 1) return fail(UNET_EINVAL, "K must be 1..64 with sweep_probs");
   for (int k = 0; k < K; ++k)
@@ -1591,54 +1627,19 @@ int unet_score(unet_handle* h, const float* logits, const void* target, int targ
   for (int c = 0; c < C; ++c) cuts.thr[c] = thresholds ? unet_logit_cut(thresholds[c]) : h->thr_logit[c];
   cuts.K = K;
   for (int k = 0; k < K; ++k) cuts.sweep[k] = unet_logit_cut(sweep_probs[k]);
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t need = score_scratch_bytes((long long)N * C, (long long)H * W, K);
-  if (need > h->score_bytes) {
-    if (stream_capturing(h, s))
-      return fail(UNET_ESTATE, "score scratch too small on a capturing stream: call unet_score_reserve first");
-    rc = grow_score(h, need);
-    if (rc) return rc;
-  }
-  order_after_last(h, s);
-  hipError_t e = launch_score(logits, target, target_kind, N, C, H, W, cuts, h->score, entries, hist, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("score launch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  rc = ensure_scratch(h, h->score, score_scratch_bytes((long long)N * C, (long long)H * W, K), stream, "score");
+  if (rc) return rc;
+  return launch_on(h, stream, "score launch", [&](hipStream_t s) {
+    return launch_score(logits, target, target_kind, N, C, H, W, cuts, h->score.p, entries, hist, s);
+  });
 }
-
-namespace {
-int loss_geometry(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
-  if ((long long)N * kMaxClasses * score_spans((long long)H * W) > 0x7FFFFFFFLL)
-    return fail(UNET_EINVAL, "N x H x W too large for one loss");
-  return UNET_OK;
-}
-// a loss scratch of at least `need` bytes
-int grow_loss(unet_handle* h, size_t need) {
-  if (need <= h->loss_bytes) return UNET_OK;
-  if (h->loss) {
-    drain(h);   // queued losses may still read the old scratch
-    (void)hipFree(h->loss);
-    h->loss = nullptr;
-    h->loss_bytes = 0;
-  }
-  hipError_t e = hipMalloc(&h->loss, need);
-  if (e != hipSuccess) {
-    h->loss = nullptr;
-    return fail(UNET_ENOMEM, std::string("loss scratch hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->loss_bytes = need;
-  return UNET_OK;
-}
-}  // namespace
 
 int unet_loss_reserve(unet_handle* h, int N, int H, int W) {
   if (!h) return fail(UNET_EINVAL, "null handle");
   const int rc = loss_geometry(N, H, W);
   if (rc) return rc;
   DeviceGuard g(h->cfg.device);
-  return grow_loss(h, loss_scratch_bytes((long long)N * kMaxClasses, (long long)H * W));
+  return grow(h, h->loss, loss_scratch_bytes((long long)N * kMaxClasses, (long long)H * W), "loss scratch");
 }
 
 int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int target_kind, int N, int C, int H, int W,
@@ -1646,61 +1647,25 @@ int unet_loss_grad(unet_handle* h, const float* logits, const void* target, int 
   // every argument check comes before the first HIP call (and before the handle is read)
   if (!h) return fail(UNET_EINVAL, "null handle");
   if (!logits || !target || !cfg || !loss) return fail(UNET_EINVAL, "logits, target, cfg and loss must not be NULL");
-  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
-  if (target_kind != UNET_TGT_F32_NCHW && target_kind != UNET_TGT_U8_NHWC)
-    return fail(UNET_EINVAL, "target_kind must be UNET_TGT_F32_NCHW or UNET_TGT_U8_NHWC");
-  int rc = loss_geometry(N, H, W);
+  int rc = check_classes(C);
+  if (!rc) rc = check_target_kind(target_kind);
+  if (!rc) rc = loss_geometry(N, H, W);
   if (rc) return rc;
   if (grad_logits == logits) return fail(UNET_EINVAL, "grad_logits must not alias logits");
   const LossParams prm{cfg->dice_weight, cfg->focal_weight, cfg->focal_alpha, cfg->smooth};
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t need = loss_scratch_bytes((long long)N * C, (long long)H * W);
-  if (need > h->loss_bytes) {
-    if (stream_capturing(h, s))
-      return fail(UNET_ESTATE, "loss scratch too small on a capturing stream: call unet_loss_reserve first");
-    rc = grow_loss(h, need);
-    if (rc) return rc;
-  }
-  order_after_last(h, s);
-  hipError_t e = launch_loss(logits, target, target_kind, N, C, H, W, prm, grad_out, loss, grad_logits, h->loss, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("loss launch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  rc = ensure_scratch(h, h->loss, loss_scratch_bytes((long long)N * C, (long long)H * W), stream, "loss");
+  if (rc) return rc;
+  return launch_on(h, stream, "loss launch", [&](hipStream_t s) {
+    return launch_loss(logits, target, target_kind, N, C, H, W, prm, grad_out, loss, grad_logits, h->loss.p, s);
+  });
 }
-
-namespace {
-int head_geometry(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return fail(UNET_EINVAL, "N, H and W must be positive");
-  if ((long long)N * head_tiles((long long)H * W) > 0x7FFFFFFFLL)
-    return fail(UNET_EINVAL, "N x H x W too large for one head call");
-  return UNET_OK;
-}
-// a head scratch of at least `need` bytes
-int grow_head(unet_handle* h, size_t need) {
-  if (need <= h->head_bytes) return UNET_OK;
-  if (h->head) {
-    drain(h);   // a queued backward may still read the old slabs
-    (void)hipFree(h->head);
-    h->head = nullptr;
-    h->head_bytes = 0;
-  }
-  hipError_t e = hipMalloc(&h->head, need);
-  if (e != hipSuccess) {
-    h->head = nullptr;
-    return fail(UNET_ENOMEM, std::string("head scratch hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->head_bytes = need;
-  return UNET_OK;
-}
-}  // namespace
 
 int unet_head_reserve(unet_handle* h, int N, int H, int W) {
   if (!h) return fail(UNET_EINVAL, "null handle");
   const int rc = head_geometry(N, H, W);
   if (rc) return rc;
   DeviceGuard g(h->cfg.device);
-  return grow_head(h, head_scratch_bytes(N, (long long)H * W, kMaxClasses));
+  return grow(h, h->head, head_scratch_bytes(N, (long long)H * W, kMaxClasses), "head scratch");
 }
 
 int unet_head_forward(unet_handle* h, const float* feat, const float* w, const float* b, float* logits, int N, int C,
@@ -1708,17 +1673,12 @@ int unet_head_forward(unet_handle* h, const float* feat, const float* w, const f
   // every argument check comes before the first HIP call (and before the handle is read)
   if (!h) return fail(UNET_EINVAL, "null handle");
   if (!feat || !w || !b || !logits) return fail(UNET_EINVAL, "feat, w, b and logits must not be NULL");
-  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
-  const int rc = head_geometry(N, H, W);
+  int rc = check_classes(C);
+  if (!rc) rc = head_geometry(N, H, W);
   if (rc) return rc;
   if (logits == feat) return fail(UNET_EINVAL, "logits must not alias feat");
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  order_after_last(h, s);
-  hipError_t e = launch_head_forward(feat, w, b, logits, N, C, H, W, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("head forward launch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  return launch_on(h, stream, "head forward launch",
+                   [&](hipStream_t s) { return launch_head_forward(feat, w, b, logits, N, C, H, W, s); });
 }
 
 int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w, float* grad_w,
@@ -1729,27 +1689,16 @@ int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logi
   if ((grad_w == nullptr) != (grad_b == nullptr))
     return fail(UNET_EINVAL, "grad_w and grad_b come as a pair: both or both NULL");
   if (!grad_w && !grad_feat) return fail(UNET_EINVAL, "no output: grad_w / grad_b and grad_feat are all NULL");
-  if (C < 1 || C > kMaxClasses) return fail(UNET_EINVAL, "C must be 1..4");
-  int rc = head_geometry(N, H, W);
+  int rc = check_classes(C);
+  if (!rc) rc = head_geometry(N, H, W);
   if (rc) return rc;
   if (grad_feat && (grad_feat == feat || grad_feat == grad_logits))
     return fail(UNET_EINVAL, "grad_feat must not alias feat or grad_logits");
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (grad_w) {
-    const size_t need = head_scratch_bytes(N, (long long)H * W, C);
-    if (need > h->head_bytes) {
-      if (stream_capturing(h, s))
-        return fail(UNET_ESTATE, "head scratch too small on a capturing stream: call unet_head_reserve first");
-      rc = grow_head(h, need);
-      if (rc) return rc;
-    }
-  }
-  order_after_last(h, s);
-  hipError_t e = launch_head_backward(feat, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W, h->head, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("head backward launch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  if (grad_w) rc = ensure_scratch(h, h->head, head_scratch_bytes(N, (long long)H * W, C), stream, "head");
+  if (rc) return rc;
+  return launch_on(h, stream, "head backward launch", [&](hipStream_t s) {
+    return launch_head_backward(feat, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W, h->head.p, s);
+  });
 }
 
 int unet_num_launches(void) { return UNET_NUM_LAUNCHES; }
@@ -1809,35 +1758,28 @@ int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel
   const size_t cnt = (size_t)N * t.C * h_ * w_;
   if (numel) *numel = cnt;
   if (!dst) return UNET_OK;
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  order_after_last(h, s);
-  // each buffer holds its consumer's operand type (the mixed plan: fp16 at levels 0-1)
-  hipError_t e = launch_nhwc_to_nchw_f32(level_dtype(h->cfg.dtype, t.level), h->ws + t.off, N, h_, w_, t.C, t.ld,
-                                         t.choff, dst, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("debug fetch: ") + hipGetErrorString(e));
-  mark_done(h, s);
-  return UNET_OK;
+  return launch_on(h, stream, "debug fetch", [&](hipStream_t s) {
+    // each buffer holds its consumer's operand type (the mixed plan: fp16 at levels 0-1)
+    return launch_nhwc_to_nchw_f32(level_dtype(h->cfg.dtype, t.level), h->ws.p + t.off, N, h_, w_, t.C, t.ld, t.choff,
+                                   dst, s);
+  });
 }
 
 namespace {
-// Every scratch allocation of the handle that exists, over its full allocated size: the forward workspace, the
-// score, loss and head scratch, the preprocess row buffer.  Not the weights, the zero page, the resample tables or
-// the mask-box sync entries (state with a defined idle value), and nothing a unet_graph owns.
+// Every scratch allocation of the handle that exists (kScratch), over its full allocated size: the forward
+// workspace, the score, loss and head scratch, the preprocess row buffer.  Not the weights, the zero page, the
+// resample tables or the mask-box sync entries (state with a defined idle value), and nothing a unet_graph owns.
 int fill_scratch(unet_handle* h, int byte, void* stream) {
-  const std::pair<void*, size_t> scratch[] = {{h->ws, h->ws_bytes}, {h->score, h->score_bytes},
-                                              {h->loss, h->loss_bytes}, {h->head, h->head_bytes},
-                                              {h->pp_tmp, h->pp_tmp_bytes}};
   bool any = false;
-  for (const auto& b : scratch) any = any || (b.first && b.second);
+  for (auto m : kScratch) any = any || (h->*m).bytes;
   if (!any) return UNET_OK;
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  order_after_last(h, s);
-  for (const auto& b : scratch)
-    if (b.first && b.second) HIP_TRY(hipMemsetAsync(b.first, byte, b.second, s));
-  mark_done(h, s);
-  return UNET_OK;
+  // (the message keeps the spelling it had when the buffers were listed as pairs)
+  return launch_on(h, stream, "hipMemsetAsync(b.first, byte, b.second, s)", [&](hipStream_t s) {
+    hipError_t e = hipSuccess;
+    for (auto m : kScratch)
+      if (e == hipSuccess && (h->*m).bytes) e = hipMemsetAsync((h->*m).p, byte, (h->*m).bytes, s);
+    return e;
+  });
 }
 }  // namespace
 
@@ -1851,33 +1793,19 @@ int unet_graph_create(unet_handle* h, const void* x, int x_layout, int x_dtype, 
                       int mask_kind, int32_t* boxes, int N, int H, int W, unet_graph** out) {
   if (!h || !out) return fail(UNET_EINVAL, "null argument");
   DeviceGuard g(h->cfg.device);
-  hipStream_t cs = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   unet_graph* gr = new unet_graph();
   gr->h = h;
-  hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-  int rc = UNET_OK;
-  if (e != hipSuccess) {
-    rc = fail(UNET_EHIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
-  } else {
-    h->capturing = true;
-    rc = forward_impl(h, x, x_layout, x_dtype, logits, masks, mask_kind, boxes, N, H, W, cs, nullptr);
-    h->capturing = false;
-    e = hipStreamEndCapture(cs, &gr->graph);
-    if (!rc && e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    if (!rc) {
-      e = hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0);
-      if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    }
-  }
-  (void)hipStreamDestroy(cs);
+  const int rc = capture(
+      h, gr, "hipStreamCreateWithFlags(&cs, hipStreamNonBlocking)", [](hipStream_t) { return (int)UNET_OK; },
+      [&](hipStream_t cs) {
+        return forward_impl(h, x, x_layout, x_dtype, logits, masks, mask_kind, boxes, N, H, W, cs, nullptr);
+      });
   if (rc) {
     if (gr->exec) (void)hipGraphExecDestroy(gr->exec);
     if (gr->graph) (void)hipGraphDestroy(gr->graph);
     delete gr;
     return rc;
   }
-  gr->generation = h->generation;
   *out = gr;
   return UNET_OK;
 }
@@ -1897,7 +1825,7 @@ int unet_photo_graph_create(unet_handle* h, const void* h_img, void* img, int ih
   int rc = check_geometry(h, 1, size, size);
   if (rc) return rc;
   if (!h->loaded) return fail(UNET_ESTATE, "weights not loaded");
-  if (plan(h, 1, size, size).total > h->ws_bytes)
+  if (plan(h, 1, size, size).total > h->ws.bytes)
     return fail(UNET_ESTATE, "workspace too small for (1, size, size): call unet_reserve first");
   DeviceGuard g(h->cfg.device);
   unet_graph* gr = new unet_graph();
@@ -1906,99 +1834,74 @@ int unet_photo_graph_create(unet_handle* h, const void* h_img, void* img, int ih
   rc = build_resample(ih, iw, size, size, gr->rs);
   const ResamplePlan& p = gr->rs.plan;
   const size_t tmp = p.need_h ? (size_t)p.h_rows * size * channels : 0;
-  if (!rc && tmp) {
-    hipError_t e = hipMalloc((void**)&gr->pp_tmp, tmp);
-    if (e != hipSuccess) rc = fail(UNET_ENOMEM, std::string("preprocess buffer: ") + hipGetErrorString(e));
-  }
+  if (!rc && tmp) rc = hip_ok(hipMalloc((void**)&gr->pp_tmp, tmp), "preprocess buffer", UNET_ENOMEM);
   const size_t sync_bytes = (size_t)h->cfg.n_classes * kSyncInts * sizeof(int);
-  if (!rc) {   // the crop sums' sync entries
-    hipError_t e = hipMalloc((void**)&gr->crop_sync, sync_bytes);
-    if (e != hipSuccess) rc = fail(UNET_ENOMEM, std::string("crop sync entries: ") + hipGetErrorString(e));
-  }
-  hipStream_t cs = nullptr;
-  if (!rc) {
-    hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
-    if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  if (!rc) {   // idle (zero) before the capture: set on the capture stream and waited for, so no replay on any
-               // caller stream can start before it (a null-stream memset is asynchronous to the host)
+  // the crop sums' sync entries
+  if (!rc) rc = hip_ok(hipMalloc((void**)&gr->crop_sync, sync_bytes), "crop sync entries", UNET_ENOMEM);
+  auto prepare = [&](hipStream_t cs) {
+    // idle (zero) before the capture: set on the capture stream and waited for, so no replay on any
+    // caller stream can start before it (a null-stream memset is asynchronous to the host)
     hipError_t e = hipMemsetAsync(gr->crop_sync, 0, sync_bytes, cs);
     if (e == hipSuccess) e = hipStreamSynchronize(cs);
-    if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("crop sync entries: ") + hipGetErrorString(e));
-  }
-  if (!rc) {
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) {
-      rc = fail(UNET_EHIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
-    } else {
-      h->capturing = true;
-      const size_t img_bytes = (size_t)ih * iw * channels;
-      const int ncls = h->cfg.n_classes;
-      // on the 16-bit plans with a vertical pass, the resize writes the fused first conv's pre-cast
-      // input straight into the workspace (one launch less; x is not written then)
-      const bool px4 = cfg_fused_in(h->L[D1B].cfg) && p.need_v;
-      void* xin = px4 ? static_cast<void*>(h->ws + plan(h, 1, size, size).xpx) : static_cast<void*>(x);
-      if (h_img) e = hipMemcpyAsync(img, h_img, img_bytes, hipMemcpyHostToDevice, cs);   // the photo upload
-      if (e == hipSuccess)
-        e = launch_resample(p, static_cast<const uint8_t*>(img), channels, gr->pp_tmp, xin, cs,
-                            px4 ? h->L[D1B].dt : DType::F32);
-      if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("photo graph upload / resize: ") + hipGetErrorString(e));
-      if (!rc)
-        rc = forward_impl(h, xin, UNET_LAYOUT_NCHW, UNET_IN_F32, nullptr, masks, mask_kind, boxes, 1, size, size, cs,
-                          nullptr, px4);
-      if (!rc) {
-        e = launch_crop_stats(static_cast<const uint8_t*>(img), ih, iw, channels, boxes, ncls, size, size, pad, rects,
-                              reinterpret_cast<unsigned long long*>(sums), gr->crop_sync, cs);
-        // the copies back, adjacent ones (device and host both contiguous) merged: each copy node
-        // costs about 4.5 us, whatever its size
-        const size_t mbytes = (size_t)ncls * size * (mask_kind == UNET_MASK_BITS ? size / 8 : size);
-        struct Copy { char* dst; const char* src; size_t bytes; };
-        std::vector<Copy> copies;
-        auto add = [&](void* dst, const void* src, size_t bytes) {
-          if (!dst) return;
-          char* d = static_cast<char*>(dst);
-          const char* sp = static_cast<const char*>(src);
-          if (!copies.empty() && copies.back().dst + copies.back().bytes == d && copies.back().src + copies.back().bytes == sp)
-            copies.back().bytes += bytes;
-          else
-            copies.push_back({d, sp, bytes});
-        };
-        // the masks copy stays a node of its own (never merged): unet_photo_graph_set_masks retargets it
-        if (h_masks && e == hipSuccess) {
-          e = hipMemcpyAsync(h_masks, masks, mbytes, hipMemcpyDeviceToHost, cs);
-          hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-          const hipGraphNode_t* deps = nullptr;
-          size_t ndeps = 0;
-          if (e == hipSuccess) e = hipStreamGetCaptureInfo_v2(cs, &st, nullptr, nullptr, &deps, &ndeps);
-          if (e == hipSuccess && ndeps == 1) {   // the node just captured
-            gr->masks_node = deps[0];
-            gr->masks_dst = h_masks;
-            gr->masks_src = masks;
-            gr->masks_bytes = mbytes;
-          }
-        }
-        add(h_boxes, boxes, (size_t)ncls * 16);
-        add(h_rects, rects, (size_t)ncls * 16);
-        add(h_sums, sums, (size_t)ncls * 8);
-        for (const Copy& c : copies)
-          if (e == hipSuccess) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, cs);
-        if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("photo graph crop stats / copies: ") + hipGetErrorString(e));
-      }
-      h->capturing = false;
-      e = hipStreamEndCapture(cs, &gr->graph);
-      if (!rc && e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-      if (!rc) {
-        e = hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0);
-        if (e != hipSuccess) rc = fail(UNET_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    return hip_ok(e, "crop sync entries");
+  };
+  auto body = [&](hipStream_t cs) {
+    const size_t img_bytes = (size_t)ih * iw * channels;
+    const int ncls = h->cfg.n_classes;
+    // on the 16-bit plans with a vertical pass, the resize writes the fused first conv's pre-cast
+    // input straight into the workspace (one launch less; x is not written then)
+    const bool px4 = cfg_fused_in(h->L[D1B].cfg) && p.need_v;
+    void* xin = px4 ? static_cast<void*>(h->ws.p + plan(h, 1, size, size).xpx) : static_cast<void*>(x);
+    hipError_t e = h_img ? hipMemcpyAsync(img, h_img, img_bytes, hipMemcpyHostToDevice, cs) : hipSuccess;   // the photo upload
+    if (e == hipSuccess)
+      e = launch_resample(p, static_cast<const uint8_t*>(img), channels, gr->pp_tmp, xin, cs,
+                          px4 ? h->L[D1B].dt : DType::F32);
+    HIP_CHECK(e, "photo graph upload / resize");
+    if (int frc = forward_impl(h, xin, UNET_LAYOUT_NCHW, UNET_IN_F32, nullptr, masks, mask_kind, boxes, 1, size, size,
+                               cs, nullptr, px4))
+      return frc;
+    e = launch_crop_stats(static_cast<const uint8_t*>(img), ih, iw, channels, boxes, ncls, size, size, pad, rects,
+                          reinterpret_cast<unsigned long long*>(sums), gr->crop_sync, cs);
+    // the copies back, adjacent ones (device and host both contiguous) merged: each copy node
+    // costs about 4.5 us, whatever its size
+    const size_t mbytes = (size_t)ncls * size * (mask_kind == UNET_MASK_BITS ? size / 8 : size);
+    struct Copy { char* dst; const char* src; size_t bytes; };
+    std::vector<Copy> copies;
+    auto add = [&](void* dst, const void* src, size_t bytes) {
+      if (!dst) return;
+      char* d = static_cast<char*>(dst);
+      const char* sp = static_cast<const char*>(src);
+      if (!copies.empty() && copies.back().dst + copies.back().bytes == d && copies.back().src + copies.back().bytes == sp)
+        copies.back().bytes += bytes;
+      else
+        copies.push_back({d, sp, bytes});
+    };
+    // the masks copy stays a node of its own (never merged): unet_photo_graph_set_masks retargets it
+    if (h_masks && e == hipSuccess) {
+      e = hipMemcpyAsync(h_masks, masks, mbytes, hipMemcpyDeviceToHost, cs);
+      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+      const hipGraphNode_t* deps = nullptr;
+      size_t ndeps = 0;
+      if (e == hipSuccess) e = hipStreamGetCaptureInfo_v2(cs, &st, nullptr, nullptr, &deps, &ndeps);
+      if (e == hipSuccess && ndeps == 1) {   // the node just captured
+        gr->masks_node = deps[0];
+        gr->masks_dst = h_masks;
+        gr->masks_src = masks;
+        gr->masks_bytes = mbytes;
       }
     }
-  }
-  if (cs) (void)hipStreamDestroy(cs);
+    add(h_boxes, boxes, (size_t)ncls * 16);
+    add(h_rects, rects, (size_t)ncls * 16);
+    add(h_sums, sums, (size_t)ncls * 8);
+    for (const Copy& c : copies)
+      if (e == hipSuccess) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, cs);
+    return hip_ok(e, "photo graph crop stats / copies");
+  };
+  if (!rc) rc = capture(h, gr, "hipStreamCreate", prepare, body);
   if (rc) {
     (void)unet_graph_destroy(gr);
     return rc;
   }
-  gr->generation = h->generation;
   *out = gr;
   return UNET_OK;
 }
@@ -2009,9 +1912,9 @@ int unet_photo_graph_set_masks(unet_graph* gr, void* h_masks) {
   if (h_masks == gr->masks_dst) return UNET_OK;
   DeviceGuard g(gr->h->cfg.device);
   // the next replay copies into h_masks; launches already enqueued keep their destination
-  hipError_t e = hipGraphExecMemcpyNodeSetParams1D(gr->exec, gr->masks_node, h_masks, gr->masks_src, gr->masks_bytes,
-                                                   hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("hipGraphExecMemcpyNodeSetParams1D: ") + hipGetErrorString(e));
+  HIP_CHECK(hipGraphExecMemcpyNodeSetParams1D(gr->exec, gr->masks_node, h_masks, gr->masks_src, gr->masks_bytes,
+                                              hipMemcpyDeviceToHost),
+            "hipGraphExecMemcpyNodeSetParams1D");
   gr->masks_dst = h_masks;
   return UNET_OK;
 }
@@ -2021,12 +1924,7 @@ int unet_graph_launch(unet_graph* gr, void* stream) {
   unet_handle* h = gr->h;
   if (gr->generation != h->generation)
     return fail(UNET_ESTATE, "graph is stale: the handle's weights or workspace were re-allocated after capture");
-  DeviceGuard g(h->cfg.device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  order_after_last(h, s);
-  HIP_TRY(hipGraphLaunch(gr->exec, s));
-  mark_done(h, s);
-  return UNET_OK;
+  return launch_on(h, stream, "hipGraphLaunch(gr->exec, s)", [&](hipStream_t s) { return hipGraphLaunch(gr->exec, s); });
 }
 
 int unet_graph_destroy(unet_graph* gr) {
@@ -2142,7 +2040,7 @@ extern "C" {
 int unet_block_create(const unet_block_config* cfg, unet_block** out) {
   if (!cfg || !out) return fail(UNET_EINVAL, "null argument");
   const int cin = cfg->in_ch, cout = cfg->out_ch;
-  if (cfg->dtype < 0 || cfg->dtype > UNET_DTYPE_F32_EXACT) return fail(UNET_EINVAL, "bad dtype");
+  if (int rc = check_dtype(cfg->dtype)) return rc;
   const bool first = cin == 1 || cin == 3;
   if (cout <= 0 || cout % 64 || (first && cout != 64) || (!first && (cin <= 0 || cin % 32)))
     return fail(UNET_ESHAPE, "DoubleConv(in_ch, out_ch) runs natively for in_ch in {1, 3} with out_ch = 64, or in_ch "
@@ -2151,9 +2049,7 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out) {
   if (!f32 && cout != 64 && cout % 128)   // the 16-bit rings tile 64 or 128-row groups
     return fail(UNET_ESHAPE, "DoubleConv(in_ch, out_ch) on the 16-bit plans needs out_ch = 64 or a multiple of 128 "
                              "(the 128-row MFMA ring tiles); fp32 takes any multiple of 64");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(UNET_EINVAL, "bad device ordinal");
+  if (int rc = check_device(cfg->device)) return rc;
   unet_block* b = new unet_block();
   b->cin = cin;
   b->cout = cout;
@@ -2207,19 +2103,7 @@ int unet_block_load_weights(unet_block* b, const unet_tensor_view* t, int n) {
   int rc = fold(sd, "b", "0", b->cin, b->cout, w, bb);
   if (!rc) rc = check_f16_range(h.L[0].dt, w, bb, "net.0");
   if (rc) return rc;
-  if (b->first) {
-    std::vector<float> wf(w.begin(), w.end()), bf(bb.begin(), bb.end());
-    rc = upload(&h, (void**)&h.w0, wf.data(), wf.size() * 4);
-    if (!rc) rc = upload(&h, (void**)&h.b0, bf.data(), bf.size() * 4);
-    h.w0p = nullptr;
-    if (!rc && h.L[0].dt != DType::F32) {
-      std::vector<uint8_t> pk;
-      pack_first_mfma(h.L[0].dt, w, b->cin, pk);
-      rc = upload(&h, &h.w0p, pk.data(), pk.size());
-    }
-  } else {
-    rc = pack3x3(&h, h.L[0], w, bb);
-  }
+  rc = b->first ? upload_first_conv(&h, h.L[0].dt, b->cin, w, bb) : pack3x3(&h, h.L[0], w, bb);
   if (rc) return rc;
   rc = fold(sd, "b", "3", b->cout, b->cout, w, bb);
   if (!rc) rc = check_f16_range(h.L[1].dt, w, bb, "net.3");
@@ -2243,14 +2127,13 @@ int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, in
   int rc = block_geometry(N, H, W);
   if (rc) return rc;
   const BlockBuffers B = block_plan(b, N, H, W);
-  if (B.total > h.ws_bytes) return fail(UNET_ESTATE, "workspace too small for this (N, H, W): call unet_block_reserve first");
+  if (B.total > h.ws.bytes) return fail(UNET_ESTATE, "workspace too small for this (N, H, W): call unet_block_reserve first");
   DeviceGuard g(h.cfg.device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   order_after_last(&h, s);
   const DType t = h.L[1].dt;
-  void* mid = h.ws + B.mid;
-  void* outb = h.ws + B.out;
-  hipError_t e = hipSuccess;
+  void* mid = h.ws.p + B.mid;
+  void* outb = h.ws.p + B.out;
   if (b->first) {
     FirstConvArgs f{};
     f.x = x;
@@ -2259,18 +2142,15 @@ int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, in
     f.b = h.b0;
     f.out = mid;
     f.N = N; f.C = b->cin; f.H = H; f.W = W;
-    e = launch_first_conv(t, f, s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("block first conv launch: ") + hipGetErrorString(e));
+    HIP_CHECK(launch_first_conv(t, f, s), "block first conv launch");
   } else {
-    e = launch_nchw_to_nhwc(t, x, N, b->cin, H, W, h.ws + B.in, s);
-    if (e != hipSuccess) return fail(UNET_EHIP, std::string("block input transpose: ") + hipGetErrorString(e));
-    rc = run_igemm(&h, -1, h.L[0], EPI_STORE, h.ws + B.in, N, H, W, b->cin, mid, b->cout, 0, nullptr, 0, s);
+    HIP_CHECK(launch_nchw_to_nhwc(t, x, N, b->cin, H, W, h.ws.p + B.in, s), "block input transpose");
+    rc = run_igemm(&h, -1, h.L[0], EPI_STORE, h.ws.p + B.in, N, H, W, b->cin, mid, b->cout, 0, nullptr, 0, s);
     if (rc) return rc;
   }
   rc = run_igemm(&h, -1, h.L[1], EPI_STORE, mid, N, H, W, b->cout, outb, b->cout, 0, nullptr, 0, s);
   if (rc) return rc;
-  e = launch_nhwc_to_nchw(t, outb, N, b->cout, H, W, y, s);
-  if (e != hipSuccess) return fail(UNET_EHIP, std::string("block output transpose: ") + hipGetErrorString(e));
+  HIP_CHECK(launch_nhwc_to_nchw(t, outb, N, b->cout, H, W, y, s), "block output transpose");
   mark_done(&h, s);
   return UNET_OK;
 }

@@ -187,6 +187,43 @@ def check(rc: int, what: str):
     raise RuntimeError(msg)
 
 
+def _ptr(t):
+    """Device (or pinned host) address of an optional tensor: None, the C side's NULL, for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _out(t: torch.Tensor | None, shape, like: torch.Tensor, what: str) -> torch.Tensor:
+    """A contiguous fp32 tensor of ``shape`` on ``like``'s device: the caller's ``t`` checked, or a fresh one."""
+    if t is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {like.device}")
+    return t
+
+
+def _scalar(t: torch.Tensor | None, like: torch.Tensor, what: str) -> None:
+    """An optional one-element fp32 tensor on ``like``'s device, of any shape."""
+    if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != like.device):
+        raise ValueError(f"{what} must be a one-element float32 tensor on {like.device}")
+
+
+def _logits_target(logits: torch.Tensor, target: torch.Tensor):
+    """(kind, n, c, h, w) of a score / loss call: logits fp32 [N, C, H, W], target fp32 [N, C, H, W] or uint8
+    [N, H, W, C], contiguous on one device."""
+    if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous float32 [N, C, H, W] device tensor")
+    n, c, h, w = logits.shape
+    if target.dtype == torch.float32:
+        kind, shape = TGT_F32_NCHW, (n, c, h, w)
+    elif target.dtype == torch.uint8:
+        kind, shape = TGT_U8_NHWC, (n, h, w, c)
+    else:
+        raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
+    if tuple(target.shape) != shape or not target.is_contiguous() or target.device != logits.device:
+        raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {logits.device}")
+    return kind, n, c, h, w
+
+
 def crop_stats(img: torch.Tensor, boxes: torch.Tensor, box_h: int, box_w: int, pad: float,
                rects: torch.Tensor, sums: torch.Tensor, stream: int) -> None:
     """unet_crop_stats: crop rectangles (int32 [n, 4]) and crop pixel sums (int64 [n]) of the mask
@@ -252,9 +289,7 @@ class Handle:
         The workspace must have been reserved for (N, H, W) (``reserve``)."""
         n, h, w, xdt = self._geometry(x, layout)
         with self.lock:
-            check(self.lib.unet_forward(self._h, x.data_ptr(), layout, xdt,
-                                        None if logits is None else logits.data_ptr(),
-                                        None if masks is None else masks.data_ptr(),
+            check(self.lib.unet_forward(self._h, x.data_ptr(), layout, xdt, _ptr(logits), _ptr(masks),
                                         mask_kind, n, h, w, stream), "unet_forward")
 
     def forward_boxes(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
@@ -264,9 +299,7 @@ class Handle:
         if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, self.n_classes, 4) or not boxes.is_contiguous():
             raise ValueError(f"boxes must be a contiguous int32 tensor of shape {(n, self.n_classes, 4)}")
         with self.lock:
-            check(self.lib.unet_forward_boxes(self._h, x.data_ptr(), layout, xdt,
-                                              None if logits is None else logits.data_ptr(),
-                                              None if masks is None else masks.data_ptr(),
+            check(self.lib.unet_forward_boxes(self._h, x.data_ptr(), layout, xdt, _ptr(logits), _ptr(masks),
                                               mask_kind, boxes.data_ptr(), n, h, w, stream), "unet_forward_boxes")
 
     def preprocess(self, img: torch.Tensor, out: torch.Tensor, stream: int) -> None:
@@ -289,17 +322,7 @@ class Handle:
         """unet_score: logits fp32 [N, C, H, W] against target fp32 [N, C, H, W] or uint8 [N, H, W, C] (device,
         contiguous).  Returns (entries, hist): device uint8 [N, C, 64] holding one ScoreEntry per (image,
         field), and device int64 [N, C, 2, K + 1] or None without ``sweep`` (K ascending probabilities)."""
-        if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
-            raise ValueError("logits must be a contiguous float32 [N, C, H, W] device tensor")
-        n, c, h, w = logits.shape
-        if target.dtype == torch.float32:
-            kind, shape = TGT_F32_NCHW, (n, c, h, w)
-        elif target.dtype == torch.uint8:
-            kind, shape = TGT_U8_NHWC, (n, h, w, c)
-        else:
-            raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
-        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != logits.device:
-            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {logits.device}")
+        kind, n, c, h, w = _logits_target(logits, target)
         thr = None
         if thresholds is not None:
             if len(thresholds) < c:
@@ -315,8 +338,7 @@ class Handle:
         entries = torch.empty((n, c, ctypes.sizeof(ScoreEntry)), device=logits.device, dtype=torch.uint8)
         with self.lock:
             check(self.lib.unet_score(self._h, logits.data_ptr(), target.data_ptr(), kind, n, c, h, w, thr,
-                                      entries.data_ptr(), probs, k, None if hist is None else hist.data_ptr(),
-                                      stream), "unet_score")
+                                      entries.data_ptr(), probs, k, _ptr(hist), stream), "unet_score")
         return entries, hist
 
     def loss_reserve(self, n: int, h: int, w: int) -> None:
@@ -332,36 +354,16 @@ class Handle:
         Returns (loss, grad): a 0-dim fp32 device tensor and the gradient at the logits, fp32 [N, C, H, W], scaled by
         ``grad_out`` (a one-element fp32 device tensor, None = 1), or None without ``want_grad``.  ``loss`` /
         ``grad``: caller-owned outputs to fill (e.g. the fixed buffers of a captured call)."""
-        if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
-            raise ValueError("logits must be a contiguous float32 [N, C, H, W] device tensor")
-        n, c, h, w = logits.shape
-        if target.dtype == torch.float32:
-            kind, shape = TGT_F32_NCHW, (n, c, h, w)
-        elif target.dtype == torch.uint8:
-            kind, shape = TGT_U8_NHWC, (n, h, w, c)
-        else:
-            raise ValueError("target must be float32 [N, C, H, W] or uint8 [N, H, W, C]")
-        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != logits.device:
-            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {logits.device}")
-        if grad_out is not None and (grad_out.dtype != torch.float32 or grad_out.numel() != 1 or
-                                     grad_out.device != logits.device):
-            raise ValueError(f"grad_out must be a one-element float32 tensor on {logits.device}")
+        kind, n, c, h, w = _logits_target(logits, target)
+        _scalar(grad_out, logits, "grad_out")
+        _scalar(loss, logits, "loss")
         if loss is None:
             loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        elif loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != logits.device:
-            raise ValueError(f"loss must be a one-element float32 tensor on {logits.device}")
-        if not want_grad:
-            grad = None
-        elif grad is None:
-            grad = torch.empty((n, c, h, w), device=logits.device, dtype=torch.float32)
-        elif (grad.dtype != torch.float32 or tuple(grad.shape) != (n, c, h, w) or not grad.is_contiguous() or
-              grad.device != logits.device):
-            raise ValueError(f"grad must be a contiguous float32 tensor of shape {(n, c, h, w)} on {logits.device}")
+        grad = _out(grad, (n, c, h, w), logits, "grad") if want_grad else None
         cfg = LossConfig(*[float(v) for v in weights])
         with self.lock:
             check(self.lib.unet_loss_grad(self._h, logits.data_ptr(), target.data_ptr(), kind, n, c, h, w,
-                                          ctypes.byref(cfg), None if grad_out is None else grad_out.data_ptr(),
-                                          loss.data_ptr(), None if grad is None else grad.data_ptr(), stream),
+                                          ctypes.byref(cfg), _ptr(grad_out), loss.data_ptr(), _ptr(grad), stream),
                   "unet_loss_grad")
         return loss, grad
 
@@ -381,21 +383,13 @@ class Handle:
         n, _, h, w = feat.shape
         return n, int(weight.shape[0]), h, w
 
-    @staticmethod
-    def _head_tensor(t: torch.Tensor | None, shape, like: torch.Tensor, what: str) -> torch.Tensor:
-        if t is None:
-            return torch.empty(shape, device=like.device, dtype=torch.float32)
-        if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != like.device:
-            raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {like.device}")
-        return t
-
     def head_forward(self, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stream: int,
                      logits: torch.Tensor | None = None) -> torch.Tensor:
         """unet_head_forward: out_conv on feat fp32 [N, 64, H, W] with weight [C, 64(, 1, 1)] and bias [C] (device,
         contiguous fp32).  Returns the logits fp32 [N, C, H, W] (``logits``: a caller-owned output to fill)."""
         n, c, h, w = self._head_operands(feat, weight)
-        bias = self._head_tensor(bias, (c,), feat, "bias")
-        logits = self._head_tensor(logits, (n, c, h, w), feat, "logits")
+        bias = _out(bias, (c,), feat, "bias")
+        logits = _out(logits, (n, c, h, w), feat, "logits")
         with self.lock:
             check(self.lib.unet_head_forward(self._h, feat.data_ptr(), weight.data_ptr(), bias.data_ptr(),
                                              logits.data_ptr(), n, c, h, w, stream), "unet_head_forward")
@@ -408,19 +402,18 @@ class Handle:
         grad_feat [N, 64, H, W]); the pair is None without ``want_params``, grad_feat without ``want_feat``.
         ``grad_w`` / ``grad_b`` / ``grad_feat``: caller-owned outputs to fill."""
         n, c, h, w = self._head_operands(feat, weight)
-        grad_logits = self._head_tensor(grad_logits, (n, c, h, w), feat, "grad_logits")
+        grad_logits = _out(grad_logits, (n, c, h, w), feat, "grad_logits")
         if not (want_params or want_feat):
             raise ValueError("head_backward: nothing to compute")
         if want_params:
-            grad_w = self._head_tensor(grad_w, (c, 64), feat, "grad_w")
-            grad_b = self._head_tensor(grad_b, (c,), feat, "grad_b")
+            grad_w = _out(grad_w, (c, 64), feat, "grad_w")
+            grad_b = _out(grad_b, (c,), feat, "grad_b")
         else:
             grad_w = grad_b = None
-        grad_feat = self._head_tensor(grad_feat, (n, 64, h, w), feat, "grad_feat") if want_feat else None
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        grad_feat = _out(grad_feat, (n, 64, h, w), feat, "grad_feat") if want_feat else None
         with self.lock:
             check(self.lib.unet_head_backward(self._h, feat.data_ptr(), grad_logits.data_ptr(), weight.data_ptr(),
-                                              ptr(grad_w), ptr(grad_b), ptr(grad_feat), n, c, h, w, stream),
+                                              _ptr(grad_w), _ptr(grad_b), _ptr(grad_feat), n, c, h, w, stream),
                   "unet_head_backward")
         return grad_w, grad_b, grad_feat
 
@@ -431,9 +424,7 @@ class Handle:
         nl = self.lib.unet_num_launches()
         ms = (ctypes.c_float * nl)()
         with self.lock:
-            check(self.lib.unet_forward_timed(self._h, x.data_ptr(), layout, xdt,
-                                              None if logits is None else logits.data_ptr(),
-                                              None if masks is None else masks.data_ptr(),
+            check(self.lib.unet_forward_timed(self._h, x.data_ptr(), layout, xdt, _ptr(logits), _ptr(masks),
                                               mask_kind, n, h, w, stream, ms), "unet_forward_timed")
         return list(ms)
 
@@ -443,11 +434,8 @@ class Handle:
         n, h, w, xdt = self._geometry(x, layout)
         g = ctypes.c_void_p()
         with self.lock:
-            check(self.lib.unet_graph_create(self._h, x.data_ptr(), layout, xdt,
-                                             None if logits is None else logits.data_ptr(),
-                                             None if masks is None else masks.data_ptr(), mask_kind,
-                                             None if boxes is None else boxes.data_ptr(), n, h, w,
-                                             ctypes.byref(g)), "unet_graph_create")
+            check(self.lib.unet_graph_create(self._h, x.data_ptr(), layout, xdt, _ptr(logits), _ptr(masks), mask_kind,
+                                             _ptr(boxes), n, h, w, ctypes.byref(g)), "unet_graph_create")
         gr = Graph(self, g, (x, logits, masks, boxes))
         self._graphs.add(gr)
         return gr
@@ -469,13 +457,12 @@ class Handle:
         if h_img is not None and h_img.numel() < img.numel():
             raise ValueError("h_img is smaller than img")
         ih, iw, c = img.shape
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         g = ctypes.c_void_p()
         with self.lock:
-            check(self.lib.unet_photo_graph_create(self._h, ptr(h_img), img.data_ptr(), ih, iw, c, x.data_ptr(), size,
-                                                   ptr(masks), mask_kind, boxes.data_ptr(), float(pad),
-                                                   rects.data_ptr(), sums.data_ptr(), ptr(h_masks), ptr(h_boxes),
-                                                   ptr(h_rects), ptr(h_sums), ctypes.byref(g)),
+            check(self.lib.unet_photo_graph_create(self._h, _ptr(h_img), img.data_ptr(), ih, iw, c, x.data_ptr(), size,
+                                                   _ptr(masks), mask_kind, boxes.data_ptr(), float(pad),
+                                                   rects.data_ptr(), sums.data_ptr(), _ptr(h_masks), _ptr(h_boxes),
+                                                   _ptr(h_rects), _ptr(h_sums), ctypes.byref(g)),
                   "unet_photo_graph_create")
         gr = Graph(self, g, (h_img, img, x, masks, boxes, rects, sums, h_masks, h_boxes, h_rects, h_sums),
                    masks_ptr=0 if h_masks is None else h_masks.data_ptr())
