@@ -144,6 +144,11 @@ int unet_forward_boxes(unet_handle* h, const void* x, int x_layout, int x_dtype,
 /* GPU preprocessing of one photo (inference.py:62-64 + preprocess, :30-44):
  * PIL Image.resize((ow, oh)) with Pillow's default BICUBIC filter -- bit-exact with Pillow's
  * fixed-point separable resampler --, convert("RGB") (gray replicated), /255 as float32, CHW.
+ * Pass order: the horizontal pass first (8-bit intermediate), then the vertical pass, as Pillow's resampler
+ * runs one resize.  One exception to "bit-exact with Image.resize": a newer Pillow's Image.resize (12.2 has the
+ * branch, 10.2 does not) resizes a photo with ih > 100 * iw that it makes less tall (oh < ih) as two one-axis
+ * resizes, the vertical one first, and its bytes then differ from this function's; such photos belong on the
+ * host (the Python drop-in's run_unet routes them there).
  * img: device uint8 HWC [ih][iw][channels], channels 3 (mode "RGB"), 1 (mode "L") or 4 (RGBX: Pillow's own
  *      in-memory layout of an "RGB" image, 4 bytes per pixel, the 4th ignored -- uploaded without repacking);
  * x:   device fp32 [3][oh][ow] (e.g. one image's slot of the unet_forward input batch).

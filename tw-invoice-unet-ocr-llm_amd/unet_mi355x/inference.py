@@ -11,7 +11,8 @@ Differences are internal only:
     on the GPU too (unet_forward_boxes); the scale / 15 % pad / crop stays on the host;
   * RGB / L photos are resized on the GPU (unet_preprocess, bit-exact with Pillow's
     BICUBIC resize), so only the original uint8 photo crosses PCIe (an RGB photo as Pillow's own
-    RGBX pixels, copied out without repacking);
+    RGBX pixels, copied out without repacking); a photo taller than 100 times its width keeps the
+    reference's host resize, as other PIL modes do (resizes_on_host);
   * for RGB / L photos the call's device work -- photo upload, resize, forward with masks and
     boxes, crop statistics and the copies back -- is one hipGraph per photo geometry
     (unet_photo_graph_create), replayed with one host call and one synchronisation.
@@ -81,6 +82,19 @@ def preprocess_array(pil_img: Image.Image) -> np.ndarray:
 def preprocess(pil_img: Image.Image) -> torch.Tensor:
     """inference.py:30-44: PIL -> Tensor [1, 3, 512, 512] fp32 on DEVICE."""
     return torch.from_numpy(preprocess_array(pil_img)).unsqueeze(0).to(DEVICE)
+
+
+def resizes_on_host(pil_img: Image.Image) -> bool:
+    """The photos whose resize stays on the host, the reference's own lines on the installed Pillow: every PIL mode
+    but RGB / L, and an RGB / L photo with H > 100 * W that the resize makes less tall.
+
+    The device resize runs the horizontal pass first and then the vertical pass, as Pillow's resampler does within
+    one resize.  A newer Pillow's ``Image.resize`` makes two one-axis resizes, the vertical one first, of exactly
+    those tall photos (12.2 does; 10.2, which the reference pins, does not): the 8-bit intermediate differs, and with
+    it most bytes.  On the host path whatever the installed Pillow does is right by construction, so no version is
+    looked at."""
+    w, h = pil_img.size
+    return pil_img.mode not in ("RGB", "L") or (h > 100 * w and h > IMG_SIZE)
 
 
 def crop_rect(box, ow: int, oh: int):
@@ -372,7 +386,7 @@ def run_unet(pil_img: Image.Image, checkpoint_path: str, compute_dtype: str | No
             st = _staging[str(DEVICE)] = _Staging(DEVICE)
     with st.lock:
         stream = torch.cuda.current_stream(st.device)
-        if pil_img.mode in ("RGB", "L"):
+        if not resizes_on_host(pil_img):
             # inference.py:63-64 (Pillow-exact BICUBIC resize + convert("RGB") + /255), the forward with the
             # fused sigmoid + threshold + per-field boxes, and the crop statistics, all on the device as
             # one graph per photo geometry: one launch, one synchronisation
@@ -392,7 +406,8 @@ def run_unet(pil_img: Image.Image, checkpoint_path: str, compute_dtype: str | No
             rects, sums = st.hr.numpy().copy(), st.hs.numpy().copy()
             masks = {k: m[i] for i, k in enumerate(FIELDS)}
             return masks, {k: crop_from_stats(pil_img, rects[i], sums[i], ch) for i, k in enumerate(FIELDS)}
-        # other PIL modes (RGBA premultiplied resize, P nearest, ...): the reference's host path
+        # other PIL modes (RGBA premultiplied resize, P nearest, ...) and photos taller than 100 times their
+        # width (resizes_on_host): the reference's host path
         x = preprocess(pil_img.resize((IMG_SIZE, IMG_SIZE)))      # inference.py:63-64
         with torch.no_grad():
             model.forward_boxes(x, masks="u8", out=(st.m, st.b))
@@ -408,7 +423,8 @@ def run_unet(pil_img: Image.Image, checkpoint_path: str, compute_dtype: str | No
 def run_unet_batch(pil_imgs, checkpoint_path: str, compute_dtype: str | None = None, exact: bool = True):
     """Batched run_unet for serving: N photos -> [(masks, crops)] in order, with run_unet's
     preprocessing, forward, masks, boxes and crop rules.  RGB / L photos are resized on the GPU
-    straight into their slot of the batch input; other PIL modes take the reference's host resize.
+    straight into their slot of the batch input; other PIL modes, and photos taller than 100 times their
+    width (``resizes_on_host``), take the reference's host resize.
 
     exact=True (default): the forward runs in chunks of at most the library's small-batch limit
     (unet_small_batch_limit, 4), the batches whose outputs are bitwise the same as at N = 1, so every
@@ -453,7 +469,7 @@ def run_unet_batch(pil_imgs, checkpoint_path: str, compute_dtype: str | None = N
 
     def launch(lo, hi):
         """Upload + resize + forward + crop statistics + copies back of photos lo .. hi-1 (asynchronous)."""
-        arrs = [photo_array(p) if p.mode in ("RGB", "L") else None for p in pil_imgs[lo:hi]]
+        arrs = [None if resizes_on_host(p) else photo_array(p) for p in pil_imgs[lo:hi]]
         offs, total = [], 0
         for a_ in arrs:
             offs.append(total)
@@ -474,7 +490,7 @@ def run_unet_batch(pil_imgs, checkpoint_path: str, compute_dtype: str | None = N
         for j in range(hi - lo):
             if imgs[j] is not None:
                 model.preprocess(imgs[j], IMG_SIZE, out=x[lo + j])
-            else:   # other PIL modes (RGBA premultiplied resize, P nearest, ...): the reference's host resize
+            else:   # other PIL modes and photos taller than 100 times their width: the reference's host resize
                 x[lo + j] = preprocess(pil_imgs[lo + j].resize((IMG_SIZE, IMG_SIZE)))[0]
         with torch.no_grad():
             model.forward_boxes(x[lo:hi], masks="u8", out=(m[lo:hi], boxes[lo:hi]))

@@ -522,7 +522,12 @@ class UNet(_Tracked, nn.Module):
         [H, W] / [H, W, 1] (L) device tensor -> fp32 [1, 3, size, size] network input, with
         Pillow's default BICUBIC resize reproduced bit-exactly (csrc/unet_preprocess.hip).
         ``out`` (optional, fp32 [3, size, size] contiguous, e.g. a slot of a batch) is filled
-        in place."""
+        in place.
+
+        The passes run horizontal first, then vertical, as Pillow's resampler runs one resize.  The one
+        exception to bit-exactness: a newer Pillow's ``Image.resize`` (12.2; not the reference's 10.2) runs the
+        vertical pass first on a photo with H > 100 * W that it makes less tall, and its bytes differ there;
+        ``run_unet`` sends such photos down the host path (``inference.resizes_on_host``)."""
         if img.dim() == 2:
             img = img.unsqueeze(-1)
         if img.device.type != "cuda":
