@@ -40,7 +40,7 @@ extern "C" {
                                     (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
                                     UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config; then
                                     unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
-                                    unet_block_debug_fill) */
+                                    unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed) */
 
 /* error codes */
 #define UNET_OK 0
@@ -381,6 +381,23 @@ int unet_head_forward(unet_handle* h, const float* feat, const float* w, const f
  * any HIP call. */
 int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w,
                        float* grad_w, float* grad_b, float* grad_feat, int N, int C, int H, int W, void* hip_stream);
+
+/* The same two calls on a feature map stored in 16 bits (a feature cache of half the size: DESIGN.md section 11).
+ * feat_dtype: UNET_DTYPE_F32 (feat is const float*, and the call runs the kernels of the untyped one),
+ * UNET_DTYPE_F16 or UNET_DTYPE_BF16 (feat is device fp16 / bf16 NCHW [N][64][H][W]); any other value, MIXED and
+ * F32_EXACT included, is UNET_EINVAL naming feat_dtype.  Each 16-bit feature is widened to fp32 once, exactly
+ * (fp16 subnormals, signed zeros, infinities and NaNs included; bf16 is a 16-bit shift), and the arithmetic above
+ * runs on the widened values: logits, grad_w, grad_b and grad_feat are, bit for bit, those of the untyped calls on
+ * the widened tensor (where a feature is NaN, a NaN in the same places).  w, b, grad_logits and every output stay
+ * fp32; the scratch is the same (unet_head_reserve does not depend on the type).  The aligned path (feat on 16
+ * bytes, H W divisible by 8) reads 16 bytes, 8 pixels, per lane; other bases and sizes read the same values with
+ * narrower loads.  Every other rule is that of the untyped calls: argument and alias checks before any HIP call,
+ * stream order, capturable after unet_head_reserve (UNET_ESTATE for growth under capture), 64-bit indices. */
+int unet_head_forward_typed(unet_handle* h, const void* feat, int feat_dtype, const float* w, const float* b,
+                            float* logits, int N, int C, int H, int W, void* hip_stream);
+int unet_head_backward_typed(unet_handle* h, const void* feat, int feat_dtype, const float* grad_logits,
+                             const float* w, float* grad_w, float* grad_b, float* grad_feat,
+                             int N, int C, int H, int W, void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

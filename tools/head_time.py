@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Time the output head's kernels (HIP events) at the headline batch: 256 x 64 x 512 x 512 fp32 features (17 GB),
-C = 3 -- unet_head_forward, unet_head_backward without and with grad_feat -- beside eager torch on the same
-tensors (F.conv2d and its autograd backward: what a user runs without them).
+C = 3 -- unet_head_forward, unet_head_backward without and with grad_feat -- beside the same forward and
+grad_w + grad_b on the features rounded to fp16 and to bf16 (unet_head_*_typed, 8.6 GB each) and beside eager torch
+on the fp32 tensors (F.conv2d and its autograd backward: what a user runs without them).
 
     python tools/head_time.py [--n 256] [--size 512] [--reps 5] [--rounds 7] [--out FILE.json]
 
 Every variant is warmed first; then ``rounds`` rounds, each timing every variant in turn (one event pair around
 ``reps`` back-to-back calls) / reps.  A figure is the median over the rounds, the spread (min .. max) beside it.
-Bytes moved, from the shapes (fp32): the forward reads feat (64 per pixel) and writes C logits; the parameter
-backward reads feat and C gradients; grad_feat reads C gradients and writes 64 more.  The yardstick is the HBM
-floor these bytes set, with eager torch beside it; no ratio is fixed in advance.  Needs a GPU with about 40 GB
-free at the default size.
+Bytes moved, from the shapes: the forward reads feat (64 elements per pixel, 4 or 2 bytes each) and writes C fp32
+logits; the parameter backward reads feat and C fp32 gradients; grad_feat reads C gradients and writes 64 fp32
+more.  The yardstick is the HBM floor these bytes set, with eager torch beside it; the 16-bit rows also carry their
+time as a fraction of the fp32 row of the same call (``vs_fp32``); no ratio is fixed in advance.  Needs a GPU with
+about 60 GB free at the default size.
 """
 import argparse
 import json
@@ -60,10 +62,27 @@ def main():
             F.conv2d(feat, w, b)
 
     px = n * s * s * 4
+    px16 = n * s * s * (64 * 2 + c * 4)   # 16-bit features, fp32 logits / gradients
+    f16 = {}
+    for name, dt in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+        f16[name] = torch.empty((n, 64, s, s), device=dev, dtype=dt)
+        for i in range(n):   # image by image, as above
+            f16[name][i] = feat[i]
+
+    def fwd16(f):
+        return lambda: h.head_forward(f, w, b, st, logits=logits)
+
+    def bwd16(f):
+        return lambda: h.head_backward(f, g, w, st, grad_w=gw, grad_b=gb)
+
     variants = [
         ("native forward", lambda: h.head_forward(feat, w, b, st, logits=logits), px * (64 + c)),
+        ("native forward, fp16 features", fwd16(f16["fp16"]), px16),
+        ("native forward, bf16 features", fwd16(f16["bf16"]), px16),
         ("native backward, no grad_feat", lambda: h.head_backward(feat, g, w, st, grad_w=gw, grad_b=gb),
          px * (64 + c)),
+        ("native backward, no grad_feat, fp16 features", bwd16(f16["fp16"]), px16),
+        ("native backward, no grad_feat, bf16 features", bwd16(f16["bf16"]), px16),
         ("native backward with grad_feat",
          lambda: h.head_backward(feat, g, w, st, want_feat=True, grad_w=gw, grad_b=gb, grad_feat=gf),
          px * (64 + c + c + 64)),
@@ -87,12 +106,15 @@ def main():
             e1.record()
             e1.synchronize()
             ms[i].append(e0.elapsed_time(e1) / a.reps)
-    rows = []
+    rows, medians = [], {}
     for (name, _, nbytes), m in zip(variants, ms):
         m.sort()
-        med = m[len(m) // 2]
+        med = medians[name] = m[len(m) // 2]
         rows.append(dict(variant=name, ms=round(med, 4), ms_min=round(m[0], 4), ms_max=round(m[-1], 4),
                          bytes_moved=nbytes, tb_per_s=round(nbytes / med / 1e9, 3)))
+        base = name.split(", fp16 features")[0].split(", bf16 features")[0]
+        if base != name:   # a 16-bit row: its time against the fp32 row of the same call (listed before it)
+            rows[-1]["vs_fp32"] = round(med / medians[base], 3)
         print(json.dumps(rows[-1]), flush=True)
     out = dict(device=torch.cuda.get_device_name(0), n=n, classes=c, size=s, reps=a.reps, rounds=a.rounds,
                results=rows)

@@ -1668,28 +1668,44 @@ int unet_head_reserve(unet_handle* h, int N, int H, int W) {
   return grow(h, h->head, head_scratch_bytes(N, (long long)H * W, kMaxClasses), "head scratch");
 }
 
-int unet_head_forward(unet_handle* h, const float* feat, const float* w, const float* b, float* logits, int N, int C,
-                      int H, int W, void* stream) {
+namespace {
+int check_feat_dtype(int feat_dtype) {
+  return feat_dtype == UNET_DTYPE_F32 || feat_dtype == UNET_DTYPE_BF16 || feat_dtype == UNET_DTYPE_F16
+             ? UNET_OK
+             : fail(UNET_EINVAL, "feat_dtype must be UNET_DTYPE_F32, UNET_DTYPE_BF16 or UNET_DTYPE_F16");
+}
+}  // namespace
+
+int unet_head_forward_typed(unet_handle* h, const void* feat, int feat_dtype, const float* w, const float* b,
+                            float* logits, int N, int C, int H, int W, void* stream) {
   // every argument check comes before the first HIP call (and before the handle is read)
   if (!h) return fail(UNET_EINVAL, "null handle");
   if (!feat || !w || !b || !logits) return fail(UNET_EINVAL, "feat, w, b and logits must not be NULL");
-  int rc = check_classes(C);
+  int rc = check_feat_dtype(feat_dtype);
+  if (!rc) rc = check_classes(C);
   if (!rc) rc = head_geometry(N, H, W);
   if (rc) return rc;
   if (logits == feat) return fail(UNET_EINVAL, "logits must not alias feat");
-  return launch_on(h, stream, "head forward launch",
-                   [&](hipStream_t s) { return launch_head_forward(feat, w, b, logits, N, C, H, W, s); });
+  return launch_on(h, stream, "head forward launch", [&](hipStream_t s) {
+    return launch_head_forward(feat, feat_dtype, w, b, logits, N, C, H, W, s);
+  });
 }
 
-int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w, float* grad_w,
-                       float* grad_b, float* grad_feat, int N, int C, int H, int W, void* stream) {
+int unet_head_forward(unet_handle* h, const float* feat, const float* w, const float* b, float* logits, int N, int C,
+                      int H, int W, void* stream) {
+  return unet_head_forward_typed(h, feat, UNET_DTYPE_F32, w, b, logits, N, C, H, W, stream);
+}
+
+int unet_head_backward_typed(unet_handle* h, const void* feat, int feat_dtype, const float* grad_logits, const float* w,
+                             float* grad_w, float* grad_b, float* grad_feat, int N, int C, int H, int W, void* stream) {
   // every argument check comes before the first HIP call (and before the handle is read)
   if (!h) return fail(UNET_EINVAL, "null handle");
   if (!feat || !grad_logits || !w) return fail(UNET_EINVAL, "feat, grad_logits and w must not be NULL");
   if ((grad_w == nullptr) != (grad_b == nullptr))
     return fail(UNET_EINVAL, "grad_w and grad_b come as a pair: both or both NULL");
   if (!grad_w && !grad_feat) return fail(UNET_EINVAL, "no output: grad_w / grad_b and grad_feat are all NULL");
-  int rc = check_classes(C);
+  int rc = check_feat_dtype(feat_dtype);
+  if (!rc) rc = check_classes(C);
   if (!rc) rc = head_geometry(N, H, W);
   if (rc) return rc;
   if (grad_feat && (grad_feat == feat || grad_feat == grad_logits))
@@ -1697,8 +1713,14 @@ int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logi
   if (grad_w) rc = ensure_scratch(h, h->head, head_scratch_bytes(N, (long long)H * W, C), stream, "head");
   if (rc) return rc;
   return launch_on(h, stream, "head backward launch", [&](hipStream_t s) {
-    return launch_head_backward(feat, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W, h->head.p, s);
+    return launch_head_backward(feat, feat_dtype, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W, h->head.p, s);
   });
+}
+
+int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logits, const float* w, float* grad_w,
+                       float* grad_b, float* grad_feat, int N, int C, int H, int W, void* stream) {
+  return unet_head_backward_typed(h, feat, UNET_DTYPE_F32, grad_logits, w, grad_w, grad_b, grad_feat, N, C, H, W,
+                                  stream);
 }
 
 int unet_num_launches(void) { return UNET_NUM_LAUNCHES; }

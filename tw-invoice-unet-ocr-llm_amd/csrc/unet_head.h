@@ -21,12 +21,17 @@ inline long long head_tiles(long long hw) { return (hw + kHeadFwdTile - 1) / kHe
 // 64 C + C fp64 partials
 size_t head_scratch_bytes(long long N, long long hw, int C);
 
+// feat / feat_dtype below: the feature map [N][64][H][W] as fp32 (UNET_DTYPE_F32), fp16 (UNET_DTYPE_F16) or bf16
+// (UNET_DTYPE_BF16); any other dtype is hipErrorInvalidValue.  A 16-bit feature is widened to fp32 exactly, then the
+// fp32 arithmetic runs: the outputs are the bits of the fp32 call on the widened tensor.
+
 // logits[n][c][p] = b[c] + sum_k w[c][k] feat[n][k][p]: one fmaf chain from the bias, k ascending
-hipError_t launch_head_forward(const float* feat, const float* w, const float* b, float* logits, int N, int C, int H,
-                               int W, hipStream_t s);
+hipError_t launch_head_forward(const void* feat, int feat_dtype, const float* w, const float* b, float* logits, int N,
+                               int C, int H, int W, hipStream_t s);
 
 // grad_w / grad_b (both or neither) through the slabs of `scratch`; grad_feat (or nullptr) element-wise
-hipError_t launch_head_backward(const float* feat, const float* g, const float* w, float* grad_w, float* grad_b,
-                                float* grad_feat, int N, int C, int H, int W, void* scratch, hipStream_t s);
+hipError_t launch_head_backward(const void* feat, int feat_dtype, const float* g, const float* w, float* grad_w,
+                                float* grad_b, float* grad_feat, int N, int C, int H, int W, void* scratch,
+                                hipStream_t s);
 
 }  // namespace unet

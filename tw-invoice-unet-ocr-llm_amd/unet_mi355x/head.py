@@ -34,10 +34,18 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def _feat(t: torch.Tensor) -> torch.Tensor:
+    """The features as the kernels read them: float16 / bfloat16 in place (contiguous in their own dtype, never
+    widened: the typed kernels widen each value in registers), every other dtype as contiguous fp32."""
+    if t.dtype in (torch.float16, torch.bfloat16):
+        return t.detach().contiguous()
+    return _f32(t)
+
+
 class _HeadConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, weight, bias, handle):
-        f, w, b = _f32(feat), _f32(weight), _f32(bias)
+        f, w, b = _feat(feat), _f32(weight), _f32(bias)
         ctx.handle = handle
         ctx.shapes = (feat.shape, weight.shape, bias.shape, feat.dtype, weight.dtype, bias.dtype)
         ctx.save_for_backward(f, w)
@@ -66,10 +74,13 @@ def head_conv(feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, hand
     """``F.conv2d(feat, weight, bias)`` for the 1x1 head on the device, with autograd.
 
     feat: [N, 64, H, W]; weight: [C, 64, 1, 1] or [C, 64] with C in 1..4; bias: [C]; all on one ROCm device
-    (a CPU tensor raises).  Non-contiguous or non-fp32 inputs are made contiguous fp32 first.  Returns the logits,
-    fp32 [N, C, H, W]: one fp32 fmaf chain per element from the bias, k ascending.  ``backward`` computes only the
-    gradients autograd asks for: grad_weight / grad_bias (fp64 sums over a fixed tree, bitwise reproducible) and
-    grad_feat.  ``handle``: the native handle to run on (default: one of this module's per device)."""
+    (a CPU tensor raises).  A float16 / bfloat16 ``feat`` is used in place -- made contiguous in its own dtype if it
+    is not, never widened to an fp32 copy, and saved for backward as it is: the kernels widen each value exactly as
+    they read it, so every output is bitwise that of the call on ``feat.float()``.  Other non-contiguous or non-fp32
+    inputs are made contiguous fp32 first.  Returns the logits, fp32 [N, C, H, W]: one fp32 fmaf chain per element
+    from the bias, k ascending.  ``backward`` computes only the gradients autograd asks for: grad_weight /
+    grad_bias (fp64 sums over a fixed tree, bitwise reproducible) and grad_feat (computed in fp32, returned in
+    ``feat``'s dtype).  ``handle``: the native handle to run on (default: one of this module's per device)."""
     for name, t in (("feat", feat), ("weight", weight), ("bias", bias)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"head_conv: {name} must be a tensor")

@@ -22,6 +22,8 @@ import torch.nn as nn
 from . import native
 
 DEFAULT_DTYPE = os.environ.get("UNET_MI355X_DTYPE", "fp32")
+# storage types of a feature map the head kernels read (features' dtype, fit_head's feature_dtype)
+_FEATURE_DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 
 # Bumped whenever a module of a UNet's tree (the _Tracked classes below) changes its parameters, buffers or
 # children -- attribute assignment, register_parameter / register_buffer / add_module, deletion -- or converts
@@ -412,14 +414,18 @@ class UNet(_Tracked, nn.Module):
         return crit.loss_and_grad(logits, target, handle=self.native_handle(logits.device))
 
     # ------------------------------------------------------------------ the output head on frozen features
-    def features(self, x: torch.Tensor) -> torch.Tensor:
+    def features(self, x: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """The 64-channel map ``out_conv`` reads (conv1's output, unet_model.py:83), fp32 [N, 64, H, W].
+        ``dtype``: ``torch.float16`` or ``torch.bfloat16`` return exactly ``features(x).to(dtype)`` (round to nearest
+        even; fp16 overflows to inf above 65504), the storage of a 16-bit feature cache (``fit_head``).
 
         The fused forward never stores it (conv1.3 and the head are one launch), so it is rebuilt from what
         the forward does store: ``conv1(cat(u1, c1))`` on the stand-alone DoubleConv, in the model's precision
         plan and with eval BatchNorm whatever the module's mode -- one forward plus one conv1 block per call,
         which a frozen backbone pays once per page.  The handle is held from the forward to the fetches, so
         another thread's forward cannot replace the intermediates in between."""
+        if dtype not in _FEATURE_DTYPES.values():
+            raise ValueError("features: dtype must be torch.float32, torch.float16 or torch.bfloat16")
         self._check_input(x)
         if x.device.type != "cuda":
             raise RuntimeError("unet_mi355x: UNet.features runs only on a ROCm GPU tensor "
@@ -441,7 +447,8 @@ class UNet(_Tracked, nn.Module):
                 h.debug_fetch_into(name, cat[i], stream)
         u1c1 = torch.cat([cat[0].view(n, 64, hh, ww), cat[1].view(n, 64, hh, ww)], 1)
         with torch.no_grad():
-            return self.conv1(u1c1)
+            feat = self.conv1(u1c1)
+        return feat if dtype == torch.float32 else feat.to(dtype)
 
     def head(self, feat: torch.Tensor) -> torch.Tensor:
         """``out_conv`` on a stored feature map (``features``' output): fp32 logits [N, n_classes, H, W], with
@@ -450,7 +457,8 @@ class UNet(_Tracked, nn.Module):
         return head_conv(feat, self.out_conv.weight, self.out_conv.bias)
 
     def fit_head(self, x: torch.Tensor, target: torch.Tensor, epochs: int = 50, batch: int = 4, lr: float = 1e-3,
-                 weight_decay: float = 1e-4, criterion=None, shuffle_seed: int | None = None) -> list:
+                 weight_decay: float = 1e-4, criterion=None, shuffle_seed: int | None = None,
+                 feature_dtype: str = "fp32") -> list:
         """Fit ``out_conv`` alone on labelled pages, the backbone frozen: a linear probe on frozen features
         (64 C + C parameters), not train.py's training -- no other parameter moves, BatchNorm runs in eval mode
         and its statistics stay.  The loop is train.py:119-160 restricted to the head: ``metrics.InvoiceLoss``,
@@ -458,7 +466,12 @@ class UNet(_Tracked, nn.Module):
 
         x: device pages [P, n_channels, H, W]; target: device fp32 [P, C, H, W] in [0, 1] or uint8 [P, H, W, C]
         (the .npy masks as stored).  The features of all pages are computed once, in chunks of ``batch``, and kept
-        on the device (P x 64 x H x W fp32; RuntimeError if that does not fit).  Batches are consecutive pages, the
+        on the device (P x 64 x H x W in ``feature_dtype``; RuntimeError if that does not fit).  ``feature_dtype``:
+        ``"fp32"``, or ``"fp16"`` / ``"bf16"`` for a cache of half the size and half the bytes per step: each chunk's
+        fp32 features are rounded to nearest even as they are stored, and the head kernels read the 16-bit cache
+        directly (bitwise the fit on the rounded features held as fp32; DESIGN.md section 11 has what the rounding
+        costs).  A non-finite value in a 16-bit cache -- a feature above 65504 stored as fp16, or a NaN from the
+        backbone -- raises RuntimeError before the first step.  Batches are consecutive pages, the
         last one possibly short, reshuffled every epoch with ``shuffle_seed`` (None: never).  Returns the
         per-epoch mean of the batch losses; the losses are summed on the device and read once per epoch.  The
         module's train / eval mode is left as found.  The next fused forward uses the new head (the weight
@@ -470,6 +483,10 @@ class UNet(_Tracked, nn.Module):
             raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
         if not isinstance(x, torch.Tensor) or not isinstance(target, torch.Tensor):
             raise TypeError("fit_head expects device tensors")
+        if feature_dtype not in _FEATURE_DTYPES:
+            raise ValueError(f"fit_head: feature_dtype must be one of {sorted(_FEATURE_DTYPES)}, "
+                             f"got {feature_dtype!r}")
+        fdt = _FEATURE_DTYPES[feature_dtype]
         if x.device.type != "cuda" or target.device != x.device:
             raise RuntimeError("unet_mi355x: fit_head runs only on ROCm GPU tensors "
                                f"(got x on {x.device}, target on {target.device}); there is no CPU fallback")
@@ -484,15 +501,20 @@ class UNet(_Tracked, nn.Module):
         weight, bias = self.out_conv.weight, self.out_conv.bias
         if not (weight.requires_grad and bias.requires_grad):
             raise RuntimeError("fit_head: out_conv's parameters must require grad")
-        need = pages * 64 * hh * ww * 4
+        need = pages * 64 * hh * ww * torch.empty((), dtype=fdt).element_size()
         with torch.cuda.device(x.device):
             free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
         if need > free:
             raise RuntimeError(f"fit_head: the feature cache of {pages} pages of {hh}x{ww} needs {need / 2**30:.2f} "
                                f"GiB, {free / 2**30:.2f} GiB are free on {x.device}; fit on fewer pages at a time")
-        feats = torch.empty((pages, 64, hh, ww), device=x.device, dtype=torch.float32)
-        for lo in range(0, pages, batch):
+        feats = torch.empty((pages, 64, hh, ww), device=x.device, dtype=fdt)
+        for lo in range(0, pages, batch):   # the fp32 transient is one chunk; the copy rounds to nearest even
             feats[lo:lo + batch] = self.features(x[lo:lo + batch])
+        # one reduction over the finished cache, read once; the fp32 cache is taken as it comes
+        if fdt != torch.float32 and not bool(torch.isfinite(feats).all()):
+            raise RuntimeError(f"fit_head: the {feature_dtype} feature cache holds non-finite values (a feature beyond "
+                               "fp16's 65504, or a NaN / inf from the backbone); use feature_dtype=\"bf16\" (fp32's "
+                               "range) or \"fp32\"")
         target = target.detach().contiguous()
         opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
         sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)

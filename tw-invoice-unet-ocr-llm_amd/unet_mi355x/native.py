@@ -23,6 +23,8 @@ UNET_OK, UNET_EINVAL, UNET_ESHAPE, UNET_ENOMEM, UNET_EHIP, UNET_ESTATE, UNET_EKE
 # "fp32": fp32 storage, every product as three bf16 terms per operand (fp32 accuracy on the bf16 MFMA pipe);
 # "fp32_exact": the same plan on the exact-fp32 MFMA
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp16": 2, "float16": 2, "mixed": 3, "fp32_exact": 4}
+# the feature types of the head calls (unet_head_*_typed's feat_dtype): torch dtype -> UNET_DTYPE_*
+HEAD_FEAT_DTYPES = {torch.float32: DTYPES["fp32"], torch.bfloat16: DTYPES["bf16"], torch.float16: DTYPES["fp16"]}
 MASK_NONE, MASK_U8, MASK_BITS = 0, 1, 2
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 COMM_ID_BYTES = 128
@@ -106,6 +108,8 @@ SIGNATURES = {
     "unet_head_reserve": (_i, [_vp, _i, _i, _i]),
     "unet_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "unet_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "unet_head_forward_typed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "unet_head_backward_typed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -374,9 +378,10 @@ class Handle:
 
     @staticmethod
     def _head_operands(feat: torch.Tensor, weight: torch.Tensor):
-        """(n, c, h, w) of a head call: feat fp32 [N, 64, H, W], weight fp32 with C x 64 elements, contiguous."""
-        if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[1] != 64 or not feat.is_contiguous():
-            raise ValueError("feat must be a contiguous float32 [N, 64, H, W] device tensor")
+        """(n, c, h, w) of a head call: feat fp32, fp16 or bf16 [N, 64, H, W], weight fp32 with C x 64 elements,
+        contiguous."""
+        if feat.dtype not in HEAD_FEAT_DTYPES or feat.dim() != 4 or feat.shape[1] != 64 or not feat.is_contiguous():
+            raise ValueError("feat must be a contiguous float32, float16 or bfloat16 [N, 64, H, W] device tensor")
         if (weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() < 2 or weight.shape[1] != 64
                 or weight.numel() != weight.shape[0] * 64 or weight.device != feat.device):
             raise ValueError(f"weight must be a contiguous float32 [C, 64] or [C, 64, 1, 1] tensor on {feat.device}")
@@ -385,22 +390,30 @@ class Handle:
 
     def head_forward(self, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stream: int,
                      logits: torch.Tensor | None = None) -> torch.Tensor:
-        """unet_head_forward: out_conv on feat fp32 [N, 64, H, W] with weight [C, 64(, 1, 1)] and bias [C] (device,
-        contiguous fp32).  Returns the logits fp32 [N, C, H, W] (``logits``: a caller-owned output to fill)."""
+        """unet_head_forward: out_conv on feat [N, 64, H, W] (contiguous float32, float16 or bfloat16; 16-bit
+        features go through unet_head_forward_typed and give the bits of the call on ``feat.float()``) with weight
+        [C, 64(, 1, 1)] and bias [C] (device, contiguous fp32).  Returns the logits fp32 [N, C, H, W] (``logits``: a
+        caller-owned output to fill)."""
         n, c, h, w = self._head_operands(feat, weight)
         bias = _out(bias, (c,), feat, "bias")
         logits = _out(logits, (n, c, h, w), feat, "logits")
         with self.lock:
-            check(self.lib.unet_head_forward(self._h, feat.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                             logits.data_ptr(), n, c, h, w, stream), "unet_head_forward")
+            if feat.dtype == torch.float32:
+                check(self.lib.unet_head_forward(self._h, feat.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                                 logits.data_ptr(), n, c, h, w, stream), "unet_head_forward")
+            else:
+                check(self.lib.unet_head_forward_typed(self._h, feat.data_ptr(), HEAD_FEAT_DTYPES[feat.dtype],
+                                                       weight.data_ptr(), bias.data_ptr(), logits.data_ptr(), n, c,
+                                                       h, w, stream), "unet_head_forward_typed")
         return logits
 
     def head_backward(self, feat: torch.Tensor, grad_logits: torch.Tensor, weight: torch.Tensor, stream: int,
                       want_params: bool = True, want_feat: bool = False, grad_w: torch.Tensor | None = None,
                       grad_b: torch.Tensor | None = None, grad_feat: torch.Tensor | None = None):
-        """unet_head_backward: from feat, grad_logits fp32 [N, C, H, W] and weight, (grad_w [C, 64], grad_b [C],
-        grad_feat [N, 64, H, W]); the pair is None without ``want_params``, grad_feat without ``want_feat``.
-        ``grad_w`` / ``grad_b`` / ``grad_feat``: caller-owned outputs to fill."""
+        """unet_head_backward: from feat (float32, float16 or bfloat16 as in ``head_forward``; 16-bit features go
+        through unet_head_backward_typed), grad_logits fp32 [N, C, H, W] and weight, (grad_w [C, 64], grad_b [C],
+        grad_feat [N, 64, H, W]), all fp32; the pair is None without ``want_params``, grad_feat without
+        ``want_feat``.  ``grad_w`` / ``grad_b`` / ``grad_feat``: caller-owned outputs to fill."""
         n, c, h, w = self._head_operands(feat, weight)
         grad_logits = _out(grad_logits, (n, c, h, w), feat, "grad_logits")
         if not (want_params or want_feat):
@@ -412,9 +425,15 @@ class Handle:
             grad_w = grad_b = None
         grad_feat = _out(grad_feat, (n, 64, h, w), feat, "grad_feat") if want_feat else None
         with self.lock:
-            check(self.lib.unet_head_backward(self._h, feat.data_ptr(), grad_logits.data_ptr(), weight.data_ptr(),
-                                              _ptr(grad_w), _ptr(grad_b), _ptr(grad_feat), n, c, h, w, stream),
-                  "unet_head_backward")
+            if feat.dtype == torch.float32:
+                check(self.lib.unet_head_backward(self._h, feat.data_ptr(), grad_logits.data_ptr(),
+                                                  weight.data_ptr(), _ptr(grad_w), _ptr(grad_b), _ptr(grad_feat), n, c,
+                                                  h, w, stream), "unet_head_backward")
+            else:
+                check(self.lib.unet_head_backward_typed(self._h, feat.data_ptr(), HEAD_FEAT_DTYPES[feat.dtype],
+                                                        grad_logits.data_ptr(), weight.data_ptr(), _ptr(grad_w),
+                                                        _ptr(grad_b), _ptr(grad_feat), n, c, h, w, stream),
+                      "unet_head_backward_typed")
         return grad_w, grad_b, grad_feat
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
