@@ -40,7 +40,8 @@ extern "C" {
                                     (still 5, symbols added only: unet_score_reserve, unet_score, unet_score_entry,
                                     UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config; then
                                     unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
-                                    unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed) */
+                                    unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed;
+                                    then unet_head_step_reserve, unet_head_step, unet_adamw_config) */
 
 /* error codes */
 #define UNET_OK 0
@@ -398,6 +399,51 @@ int unet_head_forward_typed(unet_handle* h, const void* feat, int feat_dtype, co
 int unet_head_backward_typed(unet_handle* h, const void* feat, int feat_dtype, const float* grad_logits,
                              const float* w, float* grad_w, float* grad_b, float* grad_feat,
                              int N, int C, int H, int W, void* hip_stream);
+
+/* One training step of the head from ONE pass over the stored features: what
+ * unet_head_forward_typed, unet_loss_grad, unet_head_backward_typed and an AdamW step compute in turn, without the
+ * logits or their gradient ever reaching memory, without a gathered copy of a shuffled batch, in three launches.
+ *   feat: the base of the whole feature cache, device [P][64][H][W] as feat_dtype (as unet_head_forward_typed);
+ *   target: the base of the cache's masks, device, [P][C][H][W] fp32 or [P][H][W][C] uint8 per target_kind (UNET_TGT_*);
+ *   pages: device int32 [N], the page of each of the N batch slots (any order, repeats allowed), or NULL: slot n is
+ *   page n (then N <= P).  A page outside [0, P) is never used as an address: it makes every output of the call NaN.
+ * Arithmetic: the logits are those of unet_head_forward, bit for bit; per element the fp32 chain of unet_score and
+ * the focal branch of unet_loss_grad's backward, op by op, for an upstream gradient of 1; everything after that in
+ * fp64: the gradient at a logit is (g0 e + A t + B) s, s = (1 - p) p, with A, B the Dice coefficients of its plane
+ * by unet_loss_grad's formula, so
+ *   grad_w[c][k] = sum_n ( g0 F[n][c][k] + A[n][c] T[n][c][k] + B[n][c] S[n][c][k] ),  grad_b with feat == 1,
+ *   F, T, S = sum_p of (e s, t s, s) feat[n][k][p]
+ * over a summation tree that depends on (N, H W) only, each gradient rounded to fp32 once.  loss is InvoiceLoss as
+ * unet_loss_grad returns it.  Bitwise reproducible, independent of pointer alignment, and for 16-bit features the
+ * bits of the call on the widened tensor.
+ * opt == NULL: no update; w and b are only read, grad_w [C][64] and grad_b [C] are required.  opt != NULL: state
+ * (device fp32, m_w [C][64], m_b [C], v_w [C][64], v_b [C]: 2 (64 C + C) floats, zero before step 1) is required,
+ * grad_w / grad_b become optional as a pair, and w, b and state are updated as torch.optim.AdamW does:
+ *   theta *= 1 - lr weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   theta -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * on the fp32-rounded gradient, evaluated in fp64, m, v and theta rounded to fp32 once each.  opt is read at the
+ * call (a captured step replays with the lr and step it was captured with).
+ * IEEE propagation, nothing special-cased: a NaN feature makes the loss, every gradient and every updated value
+ * NaN (it reaches all logits of its pixel, hence every plane's Dice coefficients of its page); a NaN target of class
+ * c makes the loss and grad_w[c][:], grad_b[c] (and the updated row c) NaN and leaves the other classes' bits.
+ * Stream-ordered after the handle's previous call; no host round trip; capturable after unet_head_step_reserve
+ * (the scratch, N * ceil(H W / 4096) * 199 C doubles, grows synchronously otherwise; UNET_ESTATE for growth under
+ * capture).  Bad arguments -- NULL feat, target, cfg, w, b or loss, an output that is feat, target, w or b -- are
+ * UNET_EINVAL before any HIP call. */
+typedef struct unet_adamw_config {
+  float lr, beta1, beta2, eps, weight_decay;   /* torch.optim.AdamW's: 1e-3, 0.9, 0.999, 1e-8, 1e-2 */
+  int step;                                    /* 1-based: the count of this update */
+} unet_adamw_config;
+
+/* Size the handle's head-step scratch (its own allocation: unet_workspace_bytes, unet_reserve and the other scratch
+ * buffers are unaffected) for steps of up to N batch slots of H x W with up to 4 classes.  Allocating waits for the
+ * handle's queued work. */
+int unet_head_step_reserve(unet_handle* h, int N, int H, int W);
+
+int unet_head_step(unet_handle* h, const void* feat, int feat_dtype, const void* target, int target_kind,
+                   const int32_t* pages, int P, int N, int C, int H, int W, const unet_loss_config* cfg,
+                   float* w, float* b, float* loss, float* grad_w, float* grad_b,
+                   const unet_adamw_config* opt, float* state, void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

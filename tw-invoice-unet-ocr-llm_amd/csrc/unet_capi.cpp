@@ -8,6 +8,7 @@
 #include "unet_score.h"
 #include "unet_loss.h"
 #include "unet_head.h"
+#include "unet_step.h"
 #include "../../include/unet_mi355x.h"
 
 #include <dlfcn.h>
@@ -168,6 +169,9 @@ struct unet_handle {
   // unet_head_backward's slabs (fp64 partials of grad_w / grad_b): its own allocation too, grown by
   // unet_head_reserve / unet_head_backward
   Scratch head;
+  // unet_head_step's slabs (fp64 partials of the pass) and Dice coefficients: its own allocation too, grown by
+  // unet_head_step_reserve / unet_head_step
+  Scratch step;
 };
 
 struct unet_graph {
@@ -772,8 +776,8 @@ void free_resample(ResampleStore& st) {
 }
 
 // Every scratch buffer of the handle: free_all frees and fill_scratch poisons what is listed here.
-Scratch unet_handle::*const kScratch[] = {&unet_handle::ws, &unet_handle::score, &unet_handle::loss, &unet_handle::head,
-                                          &unet_handle::pp_tmp};
+Scratch unet_handle::*const kScratch[] = {&unet_handle::ws,   &unet_handle::score, &unet_handle::loss,
+                                          &unet_handle::head, &unet_handle::step,  &unet_handle::pp_tmp};
 
 void free_all(unet_handle* h) {
   drain(h);
@@ -1595,6 +1599,7 @@ int loss_geometry(int N, int H, int W) {
   return plane_geometry(N, H, W, kMaxClasses * score_spans((long long)H * W), "loss");
 }
 int head_geometry(int N, int H, int W) { return plane_geometry(N, H, W, head_tiles((long long)H * W), "head call"); }
+int step_geometry(int N, int H, int W) { return plane_geometry(N, H, W, head_spans((long long)H * W), "head step"); }
 }  // namespace
 
 int unet_score_reserve(unet_handle* h, int N, int H, int W, int K) {
@@ -1723,6 +1728,59 @@ int unet_head_backward(unet_handle* h, const float* feat, const float* grad_logi
                                   stream);
 }
 
+int unet_head_step_reserve(unet_handle* h, int N, int H, int W) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  const int rc = step_geometry(N, H, W);
+  if (rc) return rc;
+  DeviceGuard g(h->cfg.device);
+  return grow(h, h->step, step_scratch_bytes(N, (long long)H * W, kMaxClasses), "head_step scratch");
+}
+
+int unet_head_step(unet_handle* h, const void* feat, int feat_dtype, const void* target, int target_kind,
+                   const int32_t* pages, int P, int N, int C, int H, int W, const unet_loss_config* cfg, float* w,
+                   float* b, float* loss, float* grad_w, float* grad_b, const unet_adamw_config* opt, float* state,
+                   void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!feat || !target || !cfg || !w || !b || !loss)
+    return fail(UNET_EINVAL, "feat, target, cfg, w, b and loss must not be NULL");
+  int rc = check_feat_dtype(feat_dtype);
+  if (!rc) rc = check_classes(C);
+  if (!rc) rc = check_target_kind(target_kind);
+  if (!rc) rc = step_geometry(N, H, W);
+  if (rc) return rc;
+  if (P < 1) return fail(UNET_EINVAL, "P (pages of the cache) must be positive");
+  if (!pages && N > P) return fail(UNET_EINVAL, "N exceeds P without pages");
+  if ((grad_w == nullptr) != (grad_b == nullptr))
+    return fail(UNET_EINVAL, "grad_w and grad_b come as a pair: both or both NULL");
+  if (!opt && !grad_w) return fail(UNET_EINVAL, "no output: without opt, grad_w and grad_b are required");
+  if (opt && !state) return fail(UNET_EINVAL, "opt given without state");
+  StepAdam adam{};
+  if (opt) {
+    if (opt->step < 1) return fail(UNET_EINVAL, "opt->step is 1-based");
+    if (!(opt->beta1 >= 0.0f && opt->beta1 < 1.0f && opt->beta2 >= 0.0f && opt->beta2 < 1.0f))
+      return fail(UNET_EINVAL, "opt->beta1 and opt->beta2 must lie in [0, 1)");
+    adam.on = 1;
+    adam.lr = opt->lr, adam.beta1 = opt->beta1, adam.beta2 = opt->beta2, adam.eps = opt->eps;
+    adam.decay = 1.0 - adam.lr * (double)opt->weight_decay;
+    adam.bc1 = 1.0 - std::pow(adam.beta1, (double)opt->step);
+    adam.bc2_sqrt = std::sqrt(1.0 - std::pow(adam.beta2, (double)opt->step));
+  }
+  const float* outs[] = {loss, grad_w, grad_b, state};
+  for (const float* o : outs)
+    if (o && (o == w || o == b || o == feat || o == target))
+      return fail(UNET_EINVAL, "loss, grad_w, grad_b and state must not alias feat, target, w or b");
+  if (w == b || (state && (state == loss || state == grad_w || state == grad_b)))
+    return fail(UNET_EINVAL, "w, b, state and the outputs must be distinct buffers");
+  const LossParams prm{cfg->dice_weight, cfg->focal_weight, cfg->focal_alpha, cfg->smooth};
+  rc = ensure_scratch(h, h->step, step_scratch_bytes(N, (long long)H * W, C), stream, "head_step");
+  if (rc) return rc;
+  return launch_on(h, stream, "head step launch", [&](hipStream_t s) {
+    return launch_head_step(feat, feat_dtype, target, target_kind, pages, P, N, C, H, W, prm, w, b, loss, grad_w, grad_b,
+                            adam, state, h->step.p, s);
+  });
+}
+
 int unet_num_launches(void) { return UNET_NUM_LAUNCHES; }
 
 const char* unet_launch_label(const unet_handle* h, int i) {
@@ -1789,7 +1847,7 @@ int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel
 
 namespace {
 // Every scratch allocation of the handle that exists (kScratch), over its full allocated size: the forward
-// workspace, the score, loss and head scratch, the preprocess row buffer.  Not the weights, the zero page, the
+// workspace, the score, loss, head and head-step scratch, the preprocess row buffer.  Not the weights, the zero page, the
 // resample tables or the mask-box sync entries (state with a defined idle value), and nothing a unet_graph owns.
 int fill_scratch(unet_handle* h, int byte, void* stream) {
   bool any = false;

@@ -2,7 +2,9 @@
 stored feature map, forward and backward on the native kernels (unet_head_forward / unet_head_backward,
 include/unet_mi355x.h).  With ``metrics.InvoiceLoss`` it closes the loop
 ``loss = criterion(head_conv(feat, w, b), mask); loss.backward()`` for the 64 C + C parameters of the head: a
-linear probe on frozen features (``UNet.fit_head``).  There is no CPU fallback.
+linear probe on frozen features (``UNet.fit_head``).  ``HeadFit`` is the same step as one native call: logits, loss,
+gradient and AdamW from one pass over the feature cache (unet_head_step).  There is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -97,3 +99,79 @@ def head_conv(feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, hand
     if weight.device != feat.device or bias.device != feat.device:
         raise RuntimeError("head_conv: feat, weight and bias must be on one device")
     return _HeadConvFn.apply(feat, weight, bias, handle if handle is not None else _handle(feat.device))
+
+
+class HeadFit:
+    """``loss = criterion(head_conv(feat, w, b), mask); loss.backward(); AdamW.step()`` as one native call per step
+    (unet_head_step, include/unet_mi355x.h): one pass over the features, no logits, no gathered
+    batch, three launches.  It owns AdamW's moments and step count; ``weight`` and ``bias`` stay the caller's and are
+    updated in place.
+
+    weight: contiguous fp32 [C, 64, 1, 1] or [C, 64] with C in 1..4, bias: contiguous fp32 [C], on one ROCm device
+    (tensors or parameters; autograd is not involved).  lr, betas, eps, weight_decay: torch.optim.AdamW's.
+    criterion: a ``metrics.InvoiceLoss`` whose weights to use (default: the reference's).  handle: the native handle
+    to run on (default: one of this module's per device)."""
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-4, criterion=None, handle: native.Handle | None = None):
+        from .metrics import InvoiceLoss
+        crit = criterion if criterion is not None else InvoiceLoss()
+        if not isinstance(crit, InvoiceLoss):
+            raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
+        for name, t in (("weight", weight), ("bias", bias)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"HeadFit: {name} must be a tensor")
+            if t.device.type != "cuda":
+                raise RuntimeError(f"unet_mi355x: HeadFit runs only on ROCm GPU tensors (got {name} on {t.device}); "
+                                   "there is no CPU fallback")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"HeadFit: {name} must be contiguous float32 (it is updated in place)")
+        c = weight.shape[0] if weight.dim() in (2, 4) else 0
+        if not 1 <= c <= 4 or tuple(weight.shape[1:]) not in ((64,), (64, 1, 1)):
+            raise ValueError("HeadFit expects a weight [C, 64, 1, 1] or [C, 64] with C in 1..4")
+        if tuple(bias.shape) != (c,) or bias.device != weight.device:
+            raise ValueError(f"HeadFit expects a bias [{c}] on {weight.device}")
+        self.weight, self.bias, self.n_classes = weight, bias, c
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), \
+            float(weight_decay)
+        self.loss_weights = crit.weights
+        self.handle = handle if handle is not None else _handle(weight.device)
+        self.state = torch.zeros((2 * (64 * c + c),), device=weight.device, dtype=torch.float32)   # m_w, m_b, v_w, v_b
+        self.steps = 0
+
+    def _pages(self, feats: torch.Tensor, pages):
+        """``pages`` as the kernel reads it: a device int32 tensor as it is, a host list range-checked first."""
+        if pages is None or isinstance(pages, torch.Tensor) and pages.device.type == "cuda":
+            return pages if pages is None or pages.dtype == torch.int32 else pages.to(torch.int32)
+        idx = [int(i) for i in (pages.tolist() if isinstance(pages, torch.Tensor) else pages)]
+        if not idx or min(idx) < 0 or max(idx) >= feats.shape[0]:
+            raise IndexError(f"HeadFit: pages must be a non-empty list of indices in [0, {feats.shape[0]})")
+        return torch.tensor(idx, dtype=torch.int32).to(feats.device)
+
+    def _call(self, feats, target, pages, opt, want_grads):
+        if not isinstance(feats, torch.Tensor) or feats.device != self.weight.device:
+            raise RuntimeError(f"HeadFit: feats must be a tensor on {self.weight.device}; there is no CPU fallback")
+        f = _feat(feats)
+        with torch.cuda.device(f.device):
+            return self.handle.head_step(f, target.detach().contiguous(), self.weight.detach(), self.bias.detach(),
+                                         torch.cuda.current_stream(f.device).cuda_stream,
+                                         pages=self._pages(f, pages), weights=self.loss_weights, opt=opt,
+                                         state=self.state, want_grads=want_grads)
+
+    def step(self, feats: torch.Tensor, target: torch.Tensor, pages=None, lr: float | None = None) -> torch.Tensor:
+        """One update on the batch ``pages`` (None: every page, in order) of the cache ``feats`` [P, 64, H, W] (fp32,
+        fp16 or bf16) and its masks ``target`` (fp32 [P, C, H, W] or uint8 [P, H, W, C]).  ``lr``: this step's
+        learning rate (default: the constructor's; a scheduler's value goes here).  Returns the batch's loss
+        before the update, a 0-dim fp32 device tensor.  The version counters of ``weight`` and ``bias`` move, so
+        whatever keys on them (``UNet``'s weight signature) sees the update."""
+        opt = (self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay,
+               self.steps + 1)
+        loss, _, _ = self._call(feats, target, pages, opt, False)
+        self.steps += 1
+        torch.autograd.graph.increment_version(self.weight)   # the native call wrote behind autograd's back
+        torch.autograd.graph.increment_version(self.bias)
+        return loss
+
+    def loss_and_grads(self, feats: torch.Tensor, target: torch.Tensor, pages=None):
+        """(loss, grad_w [C, 64], grad_b [C]) of the same batch, fp32 device tensors; nothing is updated."""
+        return self._call(feats, target, pages, None, True)

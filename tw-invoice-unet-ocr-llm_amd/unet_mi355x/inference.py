@@ -601,7 +601,7 @@ def evaluate(img_dir: str, mask_dir: str, checkpoint_path: str, batch: int = 4, 
 
 def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: str, epochs: int = 50,
                   batch: int = 4, lr: float = 1e-3, compute_dtype: str | None = None,
-                  feature_dtype: str = "fp32"):
+                  feature_dtype: str = "fp32", fused: bool = False):
     """Fit the output head of a checkpoint on a directory of labelled pages (``UNet.fit_head``: a linear probe
     on frozen features, e.g. for a new invoice layout) and save the result.
 
@@ -610,7 +610,8 @@ def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: s
     private cache), ``fit_head(x, masks, epochs, batch, lr, feature_dtype=feature_dtype)`` runs on all pages
     (``"fp16"`` / ``"bf16"``: a feature cache of half the size), and the full 136-key
     ``state_dict`` -- only ``out_conv.*`` differs from the checkpoint -- is written to ``out_path`` with
-    ``torch.save``.  Returns the per-epoch mean losses."""
+    ``torch.save``.  ``fused``: ``fit_head``'s, every step as one native call (unet_head_step).  Returns the
+    per-epoch mean losses."""
     if not str(DEVICE).startswith("cuda"):
         raise RuntimeError("unet_mi355x: finetune_head runs on a ROCm GPU; there is no CPU fallback")
     pages = labelled_pages(img_dir, mask_dir)
@@ -637,7 +638,7 @@ def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: s
     model = load_model(checkpoint_path, compute_dtype)
     x = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(DEVICE)
     t = torch.from_numpy(np.ascontiguousarray(np.stack(ms))).to(DEVICE)
-    losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr, feature_dtype=feature_dtype)
+    losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr, feature_dtype=feature_dtype, fused=fused)
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, out_path)
     model.close()
     return losses

@@ -458,7 +458,7 @@ class UNet(_Tracked, nn.Module):
 
     def fit_head(self, x: torch.Tensor, target: torch.Tensor, epochs: int = 50, batch: int = 4, lr: float = 1e-3,
                  weight_decay: float = 1e-4, criterion=None, shuffle_seed: int | None = None,
-                 feature_dtype: str = "fp32") -> list:
+                 feature_dtype: str = "fp32", fused: bool = False) -> list:
         """Fit ``out_conv`` alone on labelled pages, the backbone frozen: a linear probe on frozen features
         (64 C + C parameters), not train.py's training -- no other parameter moves, BatchNorm runs in eval mode
         and its statistics stay.  The loop is train.py:119-160 restricted to the head: ``metrics.InvoiceLoss``,
@@ -475,8 +475,15 @@ class UNet(_Tracked, nn.Module):
         last one possibly short, reshuffled every epoch with ``shuffle_seed`` (None: never).  Returns the
         per-epoch mean of the batch losses; the losses are summed on the device and read once per epoch.  The
         module's train / eval mode is left as found.  The next fused forward uses the new head (the weight
-        signature re-packs the handle)."""
-        from .head import head_conv
+        signature re-packs the handle).
+
+        ``fused``: run every step as one native call (``head.HeadFit``, unet_head_step: logits, loss, gradient and
+        AdamW from one pass over the batch's features) in place of head_conv + criterion +
+        torch's AdamW.  No logits are stored and a shuffled batch is not gathered: the shuffled order goes to the
+        kernel as page indices.  The learning rate of each epoch is read from torch's own
+        CosineAnnealingWarmRestarts, stepped on a stand-in optimizer.  The losses agree with the unfused loop within
+        the trajectory bar of the tests, not bitwise (the gradient is summed in another order, AdamW runs in fp64)."""
+        from .head import HeadFit, head_conv
         from .metrics import InvoiceLoss
         crit = criterion if criterion is not None else InvoiceLoss()
         if not isinstance(crit, InvoiceLoss):
@@ -516,11 +523,26 @@ class UNet(_Tracked, nn.Module):
                                "fp16's 65504, or a NaN / inf from the backbone); use feature_dtype=\"bf16\" (fp32's "
                                "range) or \"fp32\"")
         target = target.detach().contiguous()
-        opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
-        sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)
         gen = None if shuffle_seed is None else torch.Generator().manual_seed(int(shuffle_seed))
         steps = (pages + batch - 1) // batch
         losses = []
+        if fused:
+            fit = HeadFit(weight, bias, lr, weight_decay=weight_decay, criterion=crit)
+            # the schedule is torch's by construction: its scheduler on an optimizer that never steps a parameter
+            stand_in = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=lr)
+            sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(stand_in, T_0=10, T_mult=2)
+            in_order = torch.arange(pages, dtype=torch.int32, device=x.device)
+            for _ in range(epochs):
+                order = in_order if gen is None else torch.randperm(pages, generator=gen).to(x.device, torch.int32)
+                total = torch.zeros((), device=x.device, dtype=torch.float32)
+                for lo in range(0, pages, batch):
+                    total += fit.step(feats, target, order[lo:lo + batch], lr=stand_in.param_groups[0]["lr"])
+                losses.append(float(total.item()) / steps)
+                stand_in.step()
+                sched.step()
+            return losses
+        opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
+        sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)
         with torch.enable_grad():
             for _ in range(epochs):
                 order = None if gen is None else torch.randperm(pages, generator=gen).to(x.device)

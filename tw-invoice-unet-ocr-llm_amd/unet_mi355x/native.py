@@ -68,6 +68,12 @@ class LossConfig(ctypes.Structure):
                 ("smooth", ctypes.c_float)]
 
 
+class AdamWConfig(ctypes.Structure):
+    """unet_adamw_config: torch.optim.AdamW's constants and the 1-based count of the update."""
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("step", ctypes.c_int)]
+
+
 def tensor_views(state_dict):
     """state_dict (name -> torch.Tensor / np.ndarray, any device) -> (TensorView array, arrays to keep alive):
     floating tensors as contiguous host fp32 (numpy has no bfloat16: a model cast with .to(torch.bfloat16)
@@ -110,6 +116,9 @@ SIGNATURES = {
     "unet_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "unet_head_forward_typed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "unet_head_backward_typed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "unet_head_step_reserve": (_i, [_vp, _i, _i, _i]),
+    "unet_head_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(LossConfig), _vp, _vp, _vp,
+                            _vp, _vp, ctypes.POINTER(AdamWConfig), _vp, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -435,6 +444,65 @@ class Handle:
                                                         _ptr(grad_b), _ptr(grad_feat), n, c, h, w, stream),
                       "unet_head_backward_typed")
         return grad_w, grad_b, grad_feat
+
+    def head_step_reserve(self, n: int, h: int, w: int) -> None:
+        """unet_head_step_reserve: size the fused step's scratch for up to n batch slots of h x w."""
+        with self.lock:
+            check(self.lib.unet_head_step_reserve(self._h, n, h, w), "unet_head_step_reserve")
+
+    def head_step(self, feat: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stream: int,
+                  pages: torch.Tensor | None = None, weights=(0.85, 0.15, 0.8, 1.0), opt=None,
+                  state: torch.Tensor | None = None, want_grads: bool | None = None,
+                  loss: torch.Tensor | None = None, grad_w: torch.Tensor | None = None,
+                  grad_b: torch.Tensor | None = None):
+        """unet_head_step: one training step of the head from one pass over ``feat``, the whole feature cache
+        [P, 64, H, W] (contiguous float32, float16 or bfloat16), and ``target``, its masks (fp32 [P, C, H, W] or
+        uint8 [P, H, W, C]).  ``pages``: device int32 [N], the pages of the batch (None: all P pages in order).
+        ``weights`` = (dice_weight, focal_weight, focal_alpha, smooth).  ``opt``: None (no update; weight and bias are
+        only read) or (lr, beta1, beta2, eps, weight_decay, step) with ``state``, contiguous fp32 [2 (64 C + C)]
+        (m_w, m_b, v_w, v_b): weight, bias and state are then updated in place.  ``want_grads``: return the
+        gradients (default: only without ``opt``).  Returns (loss, grad_w, grad_b): a 0-dim fp32 device tensor,
+        fp32 [C, 64] and [C] (None when not asked for).  ``loss`` / ``grad_w`` / ``grad_b``: caller-owned outputs."""
+        p, c, h, w = self._head_operands(feat, weight)
+        bias = _out(bias, (c,), feat, "bias")
+        if target.dtype == torch.float32:
+            kind, shape = TGT_F32_NCHW, (p, c, h, w)
+        elif target.dtype == torch.uint8:
+            kind, shape = TGT_U8_NHWC, (p, h, w, c)
+        else:
+            raise ValueError("target must be float32 [P, C, H, W] or uint8 [P, H, W, C]")
+        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != feat.device:
+            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {feat.device}")
+        n = p
+        if pages is not None:
+            if (pages.dtype != torch.int32 or pages.dim() != 1 or pages.numel() < 1 or not pages.is_contiguous()
+                    or pages.device != feat.device):
+                raise ValueError(f"pages must be a non-empty contiguous int32 [N] tensor on {feat.device}")
+            n = pages.numel()
+        if want_grads is None:
+            want_grads = opt is None
+        if opt is None and not want_grads:
+            raise ValueError("head_step: nothing to compute")
+        cfg_opt = None
+        if opt is not None:
+            cfg_opt = AdamWConfig(*[float(v) for v in opt[:5]], int(opt[5]))
+            state = _out(state, (2 * (64 * c + c),), feat, "state")
+        _scalar(loss, feat, "loss")
+        if loss is None:
+            loss = torch.empty((), device=feat.device, dtype=torch.float32)
+        if want_grads:
+            grad_w = _out(grad_w, (c, 64), feat, "grad_w")
+            grad_b = _out(grad_b, (c,), feat, "grad_b")
+        else:
+            grad_w = grad_b = None
+        cfg = LossConfig(*[float(v) for v in weights])
+        with self.lock:
+            check(self.lib.unet_head_step(self._h, feat.data_ptr(), HEAD_FEAT_DTYPES[feat.dtype], target.data_ptr(), kind,
+                                          _ptr(pages), p, n, c, h, w, ctypes.byref(cfg), weight.data_ptr(),
+                                          bias.data_ptr(), loss.data_ptr(), _ptr(grad_w), _ptr(grad_b),
+                                          None if cfg_opt is None else ctypes.byref(cfg_opt), _ptr(state), stream),
+                  "unet_head_step")
+        return loss, grad_w, grad_b
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
                       mask_kind: int, stream: int, layout: int = LAYOUT_NCHW) -> list:
