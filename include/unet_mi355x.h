@@ -41,7 +41,8 @@ extern "C" {
                                     UNET_TGT_*; then unet_loss_reserve, unet_loss_grad, unet_loss_config; then
                                     unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
                                     unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed;
-                                    then unet_head_step_reserve, unet_head_step, unet_adamw_config) */
+                                    then unet_head_step_reserve, unet_head_step, unet_adamw_config;
+                                    then unet_head_score_reserve, unet_head_score) */
 
 /* error codes */
 #define UNET_OK 0
@@ -444,6 +445,33 @@ int unet_head_step(unet_handle* h, const void* feat, int feat_dtype, const void*
                    const int32_t* pages, int P, int N, int C, int H, int W, const unet_loss_config* cfg,
                    float* w, float* b, float* loss, float* grad_w, float* grad_b,
                    const unet_adamw_config* opt, float* state, void* hip_stream);
+
+/* Score the head from the stored features: what unet_head_forward_typed followed by
+ * unet_score computes, from ONE pass over the feature cache, without the logits ever reaching memory and without a
+ * gathered copy of the pages scored, in two launches.  Validation of a head fitted with unet_head_step.
+ *   feat, feat_dtype, target, target_kind, pages, P, N: as in unet_head_step -- the bases of the whole cache
+ *   [P][64][H][W] and of its masks, and the page of each of the N slots (device int32 [N], any order, repeats
+ *   allowed; NULL: slot n is page n, then N <= P).
+ *   w: device fp32 [C][64], b: device fp32 [C]; only read.  No weights need to be loaded into the handle.
+ *   thresholds, entries, sweep_probs, K, hist: as in unet_score; entries is [N][C] and hist [N][C][2][K+1], by slot.
+ * Arithmetic: the logits are those of unet_head_forward, bit for bit, 16-bit features widened exactly; per element
+ * the fp32 chain of unet_score, op by op; the four sums in fp64 over a summation tree that depends on H W only, the
+ * counts and bins as integers.  So n_pred, n_tgt, n_both, n_px and every bin equal unet_score's on those logits, and
+ * the sums agree to fp64 rounding (another tree).  An entry is bitwise reproducible and independent of N, of the
+ * slot, of the other slots' pages, of pointer alignment and of the feature type.
+ * A page outside [0, P) is never used as an address: that slot's four sums are NaN, its counts and bins zero and its
+ * n_px = H W; the other slots are unaffected.  A NaN feature makes the four sums of every class of its page NaN and
+ * counts as not predicted; a NaN target of class c reaches that class's sums only.
+ * Stream-ordered after the handle's previous call; no host round trip; capturable after unet_head_score_reserve (the
+ * scratch, N C ceil(H W / 4096) partials of 48 bytes and with a sweep as many rows of 2 (K + 1) uint32, grows
+ * synchronously otherwise; UNET_ESTATE for growth under capture).  unet_workspace_bytes is unaffected.  Bad arguments
+ * -- NULL feat, w, b, target or entries, entries or hist aliasing an input -- are UNET_EINVAL before any HIP call. */
+int unet_head_score_reserve(unet_handle* h, int N, int H, int W, int K);
+
+int unet_head_score(unet_handle* h, const void* feat, int feat_dtype, const float* w, const float* b,
+                    const void* target, int target_kind, const int32_t* pages, int P, int N, int C, int H, int W,
+                    const float* thresholds, unet_score_entry* entries, const float* sweep_probs, int K,
+                    int64_t* hist, void* hip_stream);
 
 int unet_destroy(unet_handle* h);
 

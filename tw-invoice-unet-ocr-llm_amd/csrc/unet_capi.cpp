@@ -9,6 +9,7 @@
 #include "unet_loss.h"
 #include "unet_head.h"
 #include "unet_step.h"
+#include "unet_hscore.h"
 #include "../../include/unet_mi355x.h"
 
 #include <dlfcn.h>
@@ -172,6 +173,9 @@ struct unet_handle {
   // unet_head_step's slabs (fp64 partials of the pass) and Dice coefficients: its own allocation too, grown by
   // unet_head_step_reserve / unet_head_step
   Scratch step;
+  // unet_head_score's partial slabs (one ScorePartial and, sweeping, one row of bins per slot, class and span): its
+  // own allocation too, grown by unet_head_score_reserve / unet_head_score
+  Scratch hscore;
 };
 
 struct unet_graph {
@@ -777,7 +781,8 @@ void free_resample(ResampleStore& st) {
 
 // Every scratch buffer of the handle: free_all frees and fill_scratch poisons what is listed here.
 Scratch unet_handle::*const kScratch[] = {&unet_handle::ws,   &unet_handle::score, &unet_handle::loss,
-                                          &unet_handle::head, &unet_handle::step,  &unet_handle::pp_tmp};
+                                          &unet_handle::head, &unet_handle::step,  &unet_handle::hscore,
+                                          &unet_handle::pp_tmp};
 
 void free_all(unet_handle* h) {
   drain(h);
@@ -1600,6 +1605,11 @@ int loss_geometry(int N, int H, int W) {
 }
 int head_geometry(int N, int H, int W) { return plane_geometry(N, H, W, head_tiles((long long)H * W), "head call"); }
 int step_geometry(int N, int H, int W) { return plane_geometry(N, H, W, head_spans((long long)H * W), "head step"); }
+int hscore_geometry(int N, int H, int W, int K) {
+  if (int rc = check_positive(N, H, W)) return rc;
+  if (K < 0 || K > kScoreMaxK) return fail(UNET_EINVAL, "K (sweep candidates) must be 0..64");
+  return check_units(N, kMaxClasses * head_spans((long long)H * W), "head score");
+}
 }  // namespace
 
 int unet_score_reserve(unet_handle* h, int N, int H, int W, int K) {
@@ -1781,6 +1791,54 @@ int unet_head_step(unet_handle* h, const void* feat, int feat_dtype, const void*
   });
 }
 
+int unet_head_score_reserve(unet_handle* h, int N, int H, int W, int K) {
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  const int rc = hscore_geometry(N, H, W, K);
+  if (rc) return rc;
+  DeviceGuard g(h->cfg.device);
+  return grow(h, h->hscore, hscore_scratch_bytes(N, (long long)H * W, kMaxClasses, K), "head_score scratch");
+}
+
+int unet_head_score(unet_handle* h, const void* feat, int feat_dtype, const float* w, const float* b,
+                    const void* target, int target_kind, const int32_t* pages, int P, int N, int C, int H, int W,
+                    const float* thresholds, unet_score_entry* entries, const float* sweep_probs, int K,
+                    int64_t* hist, void* stream) {
+  // every argument check comes before the first HIP call (and before the handle is read)
+  if (!h) return fail(UNET_EINVAL, "null handle");
+  if (!feat || !w || !b || !target || !entries)
+    return fail(UNET_EINVAL, "feat, w, b, target and entries must not be NULL");
+  int rc = check_feat_dtype(feat_dtype);
+  if (!rc) rc = check_classes(C);
+  if (!rc) rc = check_target_kind(target_kind);
+  if (rc) return rc;
+  if (hist && !sweep_probs) return fail(UNET_EINVAL, "hist given without sweep_probs");
+  if (sweep_probs && !hist) return fail(UNET_EINVAL, "sweep_probs given without hist");
+  if (!sweep_probs) K = 0;
+  rc = hscore_geometry(N, H, W, K);
+  if (rc) return rc;
+  if (sweep_probs && K < 1) return fail(UNET_EINVAL, "K must be 1..64 with sweep_probs");
+  for (int k = 0; k < K; ++k)
+    if (!(sweep_probs[k] > (k ? sweep_probs[k - 1] : -INFINITY)))   // also refuses NaN
+      return fail(UNET_EINVAL, "sweep_probs must be strictly ascending");
+  if (P < 1) return fail(UNET_EINVAL, "P (pages of the cache) must be positive");
+  if (!pages && N > P) return fail(UNET_EINVAL, "N exceeds P without pages");
+  const void* ins[] = {feat, w, b, target, pages};
+  for (const void* in : ins)
+    if (in && (in == (const void*)entries || in == (const void*)hist))
+      return fail(UNET_EINVAL, "entries and hist must not alias feat, w, b, target or pages");
+  if ((const void*)entries == (const void*)hist) return fail(UNET_EINVAL, "entries and hist must be distinct buffers");
+  ScoreCuts cuts{};
+  for (int c = 0; c < C; ++c) cuts.thr[c] = thresholds ? unet_logit_cut(thresholds[c]) : h->thr_logit[c];
+  cuts.K = K;
+  for (int k = 0; k < K; ++k) cuts.sweep[k] = unet_logit_cut(sweep_probs[k]);
+  rc = ensure_scratch(h, h->hscore, hscore_scratch_bytes(N, (long long)H * W, C, K), stream, "head_score");
+  if (rc) return rc;
+  return launch_on(h, stream, "head score launch", [&](hipStream_t s) {
+    return launch_head_score(feat, feat_dtype, w, b, target, target_kind, pages, P, N, C, H, W, cuts, h->hscore.p,
+                             entries, hist, s);
+  });
+}
+
 int unet_num_launches(void) { return UNET_NUM_LAUNCHES; }
 
 const char* unet_launch_label(const unet_handle* h, int i) {
@@ -1847,7 +1905,7 @@ int unet_debug_fetch(unet_handle* h, const char* name, float* dst, size_t* numel
 
 namespace {
 // Every scratch allocation of the handle that exists (kScratch), over its full allocated size: the forward
-// workspace, the score, loss, head and head-step scratch, the preprocess row buffer.  Not the weights, the zero page, the
+// workspace, the score, loss, head, head-step and head-score scratch, the preprocess row buffer.  Not the weights, the zero page, the
 // resample tables or the mask-box sync entries (state with a defined idle value), and nothing a unet_graph owns.
 int fill_scratch(unet_handle* h, int byte, void* stream) {
   bool any = false;

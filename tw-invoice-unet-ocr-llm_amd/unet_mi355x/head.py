@@ -101,6 +101,49 @@ def head_conv(feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, hand
     return _HeadConvFn.apply(feat, weight, bias, handle if handle is not None else _handle(feat.device))
 
 
+def _page_list(feats: torch.Tensor, pages, who: str):
+    """``pages`` as the kernels read it: a device int32 tensor as it is, a host list range-checked first."""
+    if pages is None or isinstance(pages, torch.Tensor) and pages.device.type == "cuda":
+        return pages if pages is None or pages.dtype == torch.int32 else pages.to(torch.int32)
+    idx = [int(i) for i in (pages.tolist() if isinstance(pages, torch.Tensor) else pages)]
+    if not idx or min(idx) < 0 or max(idx) >= feats.shape[0]:
+        raise IndexError(f"{who}: pages must be a non-empty list of indices in [0, {feats.shape[0]})")
+    return torch.tensor(idx, dtype=torch.int32).to(feats.device)
+
+
+def head_score(feats: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, target: torch.Tensor, pages=None,
+               thresholds=None, sweep=None, handle: native.Handle | None = None):
+    """Score the head on pages of a feature cache without forming the logits in memory (unet_head_score,
+    include/unet_mi355x.h): what ``score_logits(head_conv(feats[pages], w, b), target[pages])``
+    computes, from one pass over the cache, with no gathered copy.
+
+    feats: the cache [P, 64, H, W] (fp32, fp16 or bf16; 16-bit features are read in place); weight: fp32
+    [C, 64, 1, 1] or [C, 64] with C in 1..4; bias: fp32 [C]; target: fp32 [P, C, H, W] or uint8 [P, H, W, C]; all on
+    one ROCm device (a CPU tensor raises).  ``pages``: the pages to score, in the order of the returned entries
+    (None: all, in order) -- a host list is range-checked here (IndexError), a device tensor goes to the kernel as
+    it is, where an index outside [0, P) is never used as an address and gives that slot NaN sums.
+    ``thresholds``: C probabilities (None: the handle's); ``sweep``: up to 64 ascending probabilities.  Returns a
+    ``metrics.Score``; the 64 bytes per (page, field) and the histogram are copied to the host, which synchronises.
+    ``handle``: the native handle to run on (default: one of this module's per device)."""
+    from .metrics import Score
+    for name, t in (("feats", feats), ("weight", weight), ("bias", bias), ("target", target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"head_score: {name} must be a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"unet_mi355x: head_score runs only on ROCm GPU tensors (got {name} on {t.device}); "
+                               "there is no CPU fallback")
+    if feats.dim() != 4 or feats.shape[1] != 64:
+        raise RuntimeError("head_score expects features [P, 64, H, W]")
+    f = _feat(feats)
+    probs = None if sweep is None else [float(p) for p in sweep]
+    h = handle if handle is not None else _handle(f.device)
+    with torch.cuda.device(f.device):
+        entries, hist = h.head_score(f, target.detach().contiguous(), _f32(weight), _f32(bias),
+                                     torch.cuda.current_stream(f.device).cuda_stream,
+                                     pages=_page_list(f, pages, "head_score"), thresholds=thresholds, sweep=probs)
+    return Score(entries.cpu().numpy(), None if hist is None else hist.cpu().numpy(), probs)
+
+
 class HeadFit:
     """``loss = criterion(head_conv(feat, w, b), mask); loss.backward(); AdamW.step()`` as one native call per step
     (unet_head_step, include/unet_mi355x.h): one pass over the features, no logits, no gathered
@@ -141,12 +184,7 @@ class HeadFit:
 
     def _pages(self, feats: torch.Tensor, pages):
         """``pages`` as the kernel reads it: a device int32 tensor as it is, a host list range-checked first."""
-        if pages is None or isinstance(pages, torch.Tensor) and pages.device.type == "cuda":
-            return pages if pages is None or pages.dtype == torch.int32 else pages.to(torch.int32)
-        idx = [int(i) for i in (pages.tolist() if isinstance(pages, torch.Tensor) else pages)]
-        if not idx or min(idx) < 0 or max(idx) >= feats.shape[0]:
-            raise IndexError(f"HeadFit: pages must be a non-empty list of indices in [0, {feats.shape[0]})")
-        return torch.tensor(idx, dtype=torch.int32).to(feats.device)
+        return _page_list(feats, pages, "HeadFit")
 
     def _call(self, feats, target, pages, opt, want_grads):
         if not isinstance(feats, torch.Tensor) or feats.device != self.weight.device:

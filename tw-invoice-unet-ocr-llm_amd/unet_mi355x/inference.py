@@ -601,7 +601,8 @@ def evaluate(img_dir: str, mask_dir: str, checkpoint_path: str, batch: int = 4, 
 
 def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: str, epochs: int = 50,
                   batch: int = 4, lr: float = 1e-3, compute_dtype: str | None = None,
-                  feature_dtype: str = "fp32", fused: bool = False):
+                  feature_dtype: str = "fp32", fused: bool = False, val_fraction: float = 0.0, val_seed: int = 0,
+                  keep_best: bool = False, sweep=None, report: dict | None = None):
     """Fit the output head of a checkpoint on a directory of labelled pages (``UNet.fit_head``: a linear probe
     on frozen features, e.g. for a new invoice layout) and save the result.
 
@@ -611,9 +612,18 @@ def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: s
     (``"fp16"`` / ``"bf16"``: a feature cache of half the size), and the full 136-key
     ``state_dict`` -- only ``out_conv.*`` differs from the checkpoint -- is written to ``out_path`` with
     ``torch.save``.  ``fused``: ``fit_head``'s, every step as one native call (unet_head_step).  Returns the
-    per-epoch mean losses."""
+    per-epoch mean losses.
+
+    ``val_fraction`` > 0 holds out a random subset of ``round(val_fraction * P)`` of the P pages (at least one page
+    stays for training), drawn with ``val_seed``, as ``fit_head``'s ``val_pages``: the held-out pages are scored from
+    the feature cache after every epoch.  ``keep_best``, ``sweep`` and ``report`` are ``fit_head``'s: save the head of
+    the epoch with the lowest validation loss, choose per-field thresholds on the held-out pages, and fill the
+    caller's dict (``val_loss``, ``val_iou``, ``best_epoch``, ``heads``, ``thresholds``; also ``val_pages``, the
+    indices held out, in ``labelled_pages`` order).  With the defaults nothing is held out."""
     if not str(DEVICE).startswith("cuda"):
         raise RuntimeError("unet_mi355x: finetune_head runs on a ROCm GPU; there is no CPU fallback")
+    if not 0.0 <= val_fraction < 1.0:
+        raise ValueError("finetune_head: val_fraction must lie in [0, 1)")
     pages = labelled_pages(img_dir, mask_dir)
     if not pages:
         raise ValueError(f"no .jpg / .png pages in {img_dir}")
@@ -638,7 +648,18 @@ def finetune_head(img_dir: str, mask_dir: str, checkpoint_path: str, out_path: s
     model = load_model(checkpoint_path, compute_dtype)
     x = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(DEVICE)
     t = torch.from_numpy(np.ascontiguousarray(np.stack(ms))).to(DEVICE)
-    losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr, feature_dtype=feature_dtype, fused=fused)
+    n_val = min(int(round(val_fraction * len(pages))), len(pages) - 1)
+    if n_val < 1:
+        if keep_best or sweep is not None:
+            raise ValueError("finetune_head: keep_best and sweep need held-out pages (val_fraction)")
+        losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr, feature_dtype=feature_dtype, fused=fused)
+    else:
+        perm = torch.randperm(len(pages), generator=torch.Generator().manual_seed(int(val_seed)))
+        val_pages = sorted(perm[:n_val].tolist())
+        losses = model.fit_head(x, t, epochs=epochs, batch=batch, lr=lr, feature_dtype=feature_dtype, fused=fused,
+                                val_pages=val_pages, keep_best=keep_best, sweep=sweep, report=report)
+        if report is not None:
+            report["val_pages"] = val_pages
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, out_path)
     model.close()
     return losses

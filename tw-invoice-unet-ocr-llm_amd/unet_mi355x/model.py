@@ -456,9 +456,58 @@ class UNet(_Tracked, nn.Module):
         from .head import head_conv
         return head_conv(feat, self.out_conv.weight, self.out_conv.bias)
 
+    def feature_cache(self, x: torch.Tensor, batch: int = 4, feature_dtype: str = "fp32") -> torch.Tensor:
+        """The feature cache ``fit_head`` trains on, built once: ``features`` of all pages of ``x``
+        [P, n_channels, H, W], computed in chunks of ``batch`` and kept on the device as [P, 64, H, W] in
+        ``feature_dtype`` (``"fp32"``, or ``"fp16"`` / ``"bf16"``: each chunk's fp32 features rounded to nearest even
+        as they are stored).  RuntimeError if the cache does not fit the device's free memory, or if a 16-bit cache
+        holds a non-finite value (a feature above 65504 stored as fp16, or a NaN / inf from the backbone).  What
+        ``score_features`` and ``head.head_score`` read."""
+        if feature_dtype not in _FEATURE_DTYPES:
+            raise ValueError(f"feature_cache: feature_dtype must be one of {sorted(_FEATURE_DTYPES)}, "
+                             f"got {feature_dtype!r}")
+        fdt = _FEATURE_DTYPES[feature_dtype]
+        self._check_input(x)
+        if x.device.type != "cuda":
+            raise RuntimeError("unet_mi355x: feature_cache runs only on a ROCm GPU tensor "
+                               f"(got device {x.device}); there is no CPU fallback")
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        pages, _, hh, ww = x.shape
+        need = pages * 64 * hh * ww * torch.empty((), dtype=fdt).element_size()
+        with torch.cuda.device(x.device):
+            free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+        if need > free:
+            raise RuntimeError(f"fit_head: the feature cache of {pages} pages of {hh}x{ww} needs {need / 2**30:.2f} "
+                               f"GiB, {free / 2**30:.2f} GiB are free on {x.device}; fit on fewer pages at a time")
+        feats = torch.empty((pages, 64, hh, ww), device=x.device, dtype=fdt)
+        for lo in range(0, pages, batch):   # the fp32 transient is one chunk; the copy rounds to nearest even
+            feats[lo:lo + batch] = self.features(x[lo:lo + batch])
+        # one reduction over the finished cache, read once; the fp32 cache is taken as it comes
+        if fdt != torch.float32 and not bool(torch.isfinite(feats).all()):
+            raise RuntimeError(f"fit_head: the {feature_dtype} feature cache holds non-finite values (a feature beyond "
+                               "fp16's 65504, or a NaN / inf from the backbone); use feature_dtype=\"bf16\" (fp32's "
+                               "range) or \"fp32\"")
+        return feats
+
+    def _head_thresholds(self):
+        """The model's thresholds for its n_classes fields, padded as the native handle pads them (0.5)."""
+        return (list(self.thresholds) + [0.5] * 4)[:self.n_classes]
+
+    def score_features(self, feats: torch.Tensor, target: torch.Tensor, pages=None, sweep=None):
+        """Score ``out_conv`` on pages of a feature cache (``feature_cache``'s output, [P, 64, H, W]) against their
+        masks ``target`` (fp32 [P, C, H, W] or uint8 [P, H, W, C]) at the model's thresholds: ``head.head_score``
+        with ``out_conv``'s parameters -- what ``score`` computes for those pages, without running the backbone
+        again, without storing logits and without gathering ``pages`` (None: all, in order) out of the cache.
+        Returns a ``metrics.Score``, one entry per listed page."""
+        from .head import head_score
+        return head_score(feats, self.out_conv.weight, self.out_conv.bias, target, pages=pages,
+                          thresholds=self._head_thresholds(), sweep=sweep)
+
     def fit_head(self, x: torch.Tensor, target: torch.Tensor, epochs: int = 50, batch: int = 4, lr: float = 1e-3,
                  weight_decay: float = 1e-4, criterion=None, shuffle_seed: int | None = None,
-                 feature_dtype: str = "fp32", fused: bool = False) -> list:
+                 feature_dtype: str = "fp32", fused: bool = False, val_pages=None, keep_best: bool = False,
+                 sweep=None, report: dict | None = None) -> list:
         """Fit ``out_conv`` alone on labelled pages, the backbone frozen: a linear probe on frozen features
         (64 C + C parameters), not train.py's training -- no other parameter moves, BatchNorm runs in eval mode
         and its statistics stay.  The loop is train.py:119-160 restricted to the head: ``metrics.InvoiceLoss``,
@@ -466,7 +515,8 @@ class UNet(_Tracked, nn.Module):
 
         x: device pages [P, n_channels, H, W]; target: device fp32 [P, C, H, W] in [0, 1] or uint8 [P, H, W, C]
         (the .npy masks as stored).  The features of all pages are computed once, in chunks of ``batch``, and kept
-        on the device (P x 64 x H x W in ``feature_dtype``; RuntimeError if that does not fit).  ``feature_dtype``:
+        on the device (``feature_cache``: P x 64 x H x W in ``feature_dtype``; RuntimeError if that does not fit).
+        ``feature_dtype``:
         ``"fp32"``, or ``"fp16"`` / ``"bf16"`` for a cache of half the size and half the bytes per step: each chunk's
         fp32 features are rounded to nearest even as they are stored, and the head kernels read the 16-bit cache
         directly (bitwise the fit on the rounded features held as fp32; DESIGN.md section 11 has what the rounding
@@ -482,9 +532,22 @@ class UNet(_Tracked, nn.Module):
         torch's AdamW.  No logits are stored and a shuffled batch is not gathered: the shuffled order goes to the
         kernel as page indices.  The learning rate of each epoch is read from torch's own
         CosineAnnealingWarmRestarts, stepped on a stand-in optimizer.  The losses agree with the unfused loop within
-        the trajectory bar of the tests, not bitwise (the gradient is summed in another order, AdamW runs in fp64)."""
-        from .head import HeadFit, head_conv
-        from .metrics import InvoiceLoss
+        the trajectory bar of the tests, not bitwise (the gradient is summed in another order, AdamW runs in fp64).
+
+        Validation, the other half of train.py:129-160.  ``val_pages``: distinct page
+        indices into ``x``, held out: training runs on the other pages in ascending order (reshuffled per epoch as
+        ``train_idx[randperm(len(train_idx))]``), and after every epoch the held-out pages are scored from the cache
+        in one native call (unet_head_score) at the model's thresholds.  The entries and the head of every epoch
+        stay on the device and are read once after the last epoch: validation adds no host synchronisation.
+        ``keep_best``: leave in ``out_conv`` the head of the epoch with the lowest validation ``Score.loss()`` (the
+        criterion's weights), the first on ties, instead of the last epoch's.  ``sweep``: ascending probabilities for
+        one final sweep of the held-out pages with the head that is kept.  ``report``: a dict to fill with
+        ``val_loss`` (list of floats), ``val_iou`` ([epochs][C] pooled IoU), ``best_epoch``, ``heads`` (the
+        [epochs][65 C] array: weight then bias) and, with ``sweep``, ``thresholds`` (``Score.best_thresholds()``).
+        ``keep_best`` and ``sweep`` need ``val_pages``.  Without ``val_pages`` the fit is what it was."""
+        import numpy as np
+        from .head import HeadFit, _handle, head_conv
+        from .metrics import InvoiceLoss, Score
         crit = criterion if criterion is not None else InvoiceLoss()
         if not isinstance(crit, InvoiceLoss):
             raise TypeError("criterion must be a unet_mi355x.metrics.InvoiceLoss")
@@ -493,7 +556,24 @@ class UNet(_Tracked, nn.Module):
         if feature_dtype not in _FEATURE_DTYPES:
             raise ValueError(f"fit_head: feature_dtype must be one of {sorted(_FEATURE_DTYPES)}, "
                              f"got {feature_dtype!r}")
-        fdt = _FEATURE_DTYPES[feature_dtype]
+        val = train = None
+        if val_pages is not None:   # host lists, checked before any device work
+            val = [int(i) for i in (val_pages.tolist() if isinstance(val_pages, torch.Tensor) else val_pages)]
+            total = x.shape[0] if x.dim() else 0
+            if not val:
+                raise ValueError("fit_head: val_pages is empty (None: no validation)")
+            if len(set(val)) != len(val):
+                raise ValueError("fit_head: val_pages repeats a page")
+            if min(val) < 0 or max(val) >= total:
+                raise IndexError(f"fit_head: val_pages must be indices in [0, {total})")
+            held = set(val)
+            train = [i for i in range(total) if i not in held]
+            if not train:
+                raise ValueError("fit_head: val_pages leaves no page for training")
+        elif keep_best or sweep is not None:
+            raise ValueError("fit_head: keep_best and sweep need val_pages")
+        if report is not None and not isinstance(report, dict):
+            raise TypeError("fit_head: report must be a dict")
         if x.device.type != "cuda" or target.device != x.device:
             raise RuntimeError("unet_mi355x: fit_head runs only on ROCm GPU tensors "
                                f"(got x on {x.device}, target on {target.device}); there is no CPU fallback")
@@ -508,57 +588,96 @@ class UNet(_Tracked, nn.Module):
         weight, bias = self.out_conv.weight, self.out_conv.bias
         if not (weight.requires_grad and bias.requires_grad):
             raise RuntimeError("fit_head: out_conv's parameters must require grad")
-        need = pages * 64 * hh * ww * torch.empty((), dtype=fdt).element_size()
-        with torch.cuda.device(x.device):
-            free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-        if need > free:
-            raise RuntimeError(f"fit_head: the feature cache of {pages} pages of {hh}x{ww} needs {need / 2**30:.2f} "
-                               f"GiB, {free / 2**30:.2f} GiB are free on {x.device}; fit on fewer pages at a time")
-        feats = torch.empty((pages, 64, hh, ww), device=x.device, dtype=fdt)
-        for lo in range(0, pages, batch):   # the fp32 transient is one chunk; the copy rounds to nearest even
-            feats[lo:lo + batch] = self.features(x[lo:lo + batch])
-        # one reduction over the finished cache, read once; the fp32 cache is taken as it comes
-        if fdt != torch.float32 and not bool(torch.isfinite(feats).all()):
-            raise RuntimeError(f"fit_head: the {feature_dtype} feature cache holds non-finite values (a feature beyond "
-                               "fp16's 65504, or a NaN / inf from the backbone); use feature_dtype=\"bf16\" (fp32's "
-                               "range) or \"fp32\"")
+        feats = self.feature_cache(x, batch, feature_dtype)
         target = target.detach().contiguous()
         gen = None if shuffle_seed is None else torch.Generator().manual_seed(int(shuffle_seed))
-        steps = (pages + batch - 1) // batch
+        n_train = pages if train is None else len(train)
+        train_host = None if train is None else torch.tensor(train, dtype=torch.int64)
+        steps = (n_train + batch - 1) // batch
+
+        def shuffled():   # this epoch's pages on the host: randperm, through the training pages when some are held out
+            perm = torch.randperm(n_train, generator=gen)
+            return perm if train_host is None else train_host[perm]
+
+        validate = None
+        if val is not None:
+            vh = _handle(x.device)
+            val_dev = torch.tensor(val, dtype=torch.int32).to(x.device)
+            val_entries = torch.empty((epochs, len(val), c, native.SCORE_DTYPE.itemsize), device=x.device,
+                                      dtype=torch.uint8)
+            heads = torch.empty((epochs, 65 * c), device=x.device, dtype=torch.float32)
+            thr = self._head_thresholds()
+            with torch.cuda.device(x.device):
+                vh.head_score_reserve(len(val), hh, ww, 0 if sweep is None else len(sweep))
+
+            def validate(ep):   # one native call and two small copies on the stream; nothing is read here
+                with torch.cuda.device(x.device):
+                    vh.head_score(feats, target, weight.detach(), bias.detach(),
+                                  torch.cuda.current_stream(x.device).cuda_stream, pages=val_dev, thresholds=thr,
+                                  entries=val_entries[ep])
+                heads[ep, :64 * c].copy_(weight.detach().reshape(-1))
+                heads[ep, 64 * c:].copy_(bias.detach())
+
         losses = []
         if fused:
             fit = HeadFit(weight, bias, lr, weight_decay=weight_decay, criterion=crit)
             # the schedule is torch's by construction: its scheduler on an optimizer that never steps a parameter
             stand_in = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=lr)
             sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(stand_in, T_0=10, T_mult=2)
-            in_order = torch.arange(pages, dtype=torch.int32, device=x.device)
-            for _ in range(epochs):
-                order = in_order if gen is None else torch.randperm(pages, generator=gen).to(x.device, torch.int32)
+            in_order = (torch.arange(pages, dtype=torch.int32, device=x.device) if train_host is None
+                        else train_host.to(x.device, torch.int32))
+            for ep in range(epochs):
+                order = in_order if gen is None else shuffled().to(x.device, torch.int32)
                 total = torch.zeros((), device=x.device, dtype=torch.float32)
-                for lo in range(0, pages, batch):
+                for lo in range(0, n_train, batch):
                     total += fit.step(feats, target, order[lo:lo + batch], lr=stand_in.param_groups[0]["lr"])
+                if validate is not None:
+                    validate(ep)
                 losses.append(float(total.item()) / steps)
                 stand_in.step()
                 sched.step()
+        else:
+            opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
+            sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)
+            in_order = None if train_host is None else train_host.to(x.device)
+            with torch.enable_grad():
+                for ep in range(epochs):
+                    order = in_order if gen is None else shuffled().to(x.device)
+                    total = torch.zeros((), device=x.device, dtype=torch.float32)
+                    for lo in range(0, n_train, batch):
+                        if order is None:
+                            f, t = feats[lo:lo + batch], target[lo:lo + batch]
+                        else:
+                            f, t = feats[order[lo:lo + batch]], target[order[lo:lo + batch]]
+                        loss = crit(head_conv(f, weight, bias), t)
+                        opt.zero_grad()
+                        loss.backward()
+                        opt.step()
+                        total += loss.detach()
+                    if validate is not None:
+                        validate(ep)
+                    losses.append(float(total.item()) / steps)
+                    sched.step()
+        if val is None:
             return losses
-        opt = torch.optim.AdamW([weight, bias], lr=lr, weight_decay=weight_decay)
-        sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, T_mult=2)
-        with torch.enable_grad():
-            for _ in range(epochs):
-                order = None if gen is None else torch.randperm(pages, generator=gen).to(x.device)
-                total = torch.zeros((), device=x.device, dtype=torch.float32)
-                for lo in range(0, pages, batch):
-                    if order is None:
-                        f, t = feats[lo:lo + batch], target[lo:lo + batch]
-                    else:
-                        f, t = feats[order[lo:lo + batch]], target[order[lo:lo + batch]]
-                    loss = crit(head_conv(f, weight, bias), t)
-                    opt.zero_grad()
-                    loss.backward()
-                    opt.step()
-                    total += loss.detach()
-                losses.append(float(total.item()) / steps)
-                sched.step()
+        # the one read of the validation record
+        entries, heads_host = val_entries.cpu().numpy(), heads.cpu().numpy()
+        dw, fw, alpha, smooth = crit.weights
+        scores = [Score(entries[ep]) for ep in range(epochs)]
+        val_loss = [s.loss(dw, fw, None, smooth, alpha) for s in scores]
+        finite = [v for v in val_loss if v == v]   # a NaN loss never wins; all NaN: the last epoch stays
+        best = val_loss.index(min(finite)) if finite else epochs - 1
+        if keep_best and best != epochs - 1:
+            with torch.no_grad():
+                weight.copy_(heads[best, :64 * c].view_as(weight))
+                bias.copy_(heads[best, 64 * c:])
+        if report is not None:
+            report["val_loss"] = val_loss
+            report["val_iou"] = np.stack([s.pooled_iou() for s in scores])
+            report["best_epoch"] = best
+            report["heads"] = heads_host
+            if sweep is not None:
+                report["thresholds"] = self.score_features(feats, target, pages=val, sweep=sweep).best_thresholds()
         return losses
 
     def preprocess(self, img: torch.Tensor, size: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:

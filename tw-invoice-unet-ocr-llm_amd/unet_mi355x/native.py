@@ -119,6 +119,9 @@ SIGNATURES = {
     "unet_head_step_reserve": (_i, [_vp, _i, _i, _i]),
     "unet_head_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(LossConfig), _vp, _vp, _vp,
                             _vp, _vp, ctypes.POINTER(AdamWConfig), _vp, _vp]),
+    "unet_head_score_reserve": (_i, [_vp, _i, _i, _i, _i]),
+    "unet_head_score": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float),
+                             _vp, ctypes.POINTER(ctypes.c_float), _i, _vp, _vp]),
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
@@ -503,6 +506,61 @@ class Handle:
                                           None if cfg_opt is None else ctypes.byref(cfg_opt), _ptr(state), stream),
                   "unet_head_step")
         return loss, grad_w, grad_b
+
+    def head_score_reserve(self, n: int, h: int, w: int, k: int = 0) -> None:
+        """unet_head_score_reserve: size the head score's scratch for up to n batch slots of h x w and k sweep
+        candidates."""
+        with self.lock:
+            check(self.lib.unet_head_score_reserve(self._h, n, h, w, k), "unet_head_score_reserve")
+
+    def head_score(self, feat: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, stream: int,
+                   pages: torch.Tensor | None = None, thresholds=None, sweep=None,
+                   entries: torch.Tensor | None = None):
+        """unet_head_score: out_conv's logits scored where they are formed, from one pass over ``feat``, the whole
+        feature cache [P, 64, H, W] (contiguous float32, float16 or bfloat16), and ``target``, its masks (fp32
+        [P, C, H, W] or uint8 [P, H, W, C]).  ``pages``: device int32 [N], the pages to score (None: all P pages in
+        order).  ``thresholds``: C probabilities (None: the handle's); ``sweep``: K ascending probabilities.
+        Returns (entries, hist) as ``score`` does, by slot: device uint8 [N, C, 64] and device int64
+        [N, C, 2, K + 1] or None.  ``entries``: a caller-owned output to fill (contiguous uint8 [N, C, 64])."""
+        p, c, h, w = self._head_operands(feat, weight)
+        bias = _out(bias, (c,), feat, "bias")
+        if target.dtype == torch.float32:
+            kind, shape = TGT_F32_NCHW, (p, c, h, w)
+        elif target.dtype == torch.uint8:
+            kind, shape = TGT_U8_NHWC, (p, h, w, c)
+        else:
+            raise ValueError("target must be float32 [P, C, H, W] or uint8 [P, H, W, C]")
+        if tuple(target.shape) != shape or not target.is_contiguous() or target.device != feat.device:
+            raise ValueError(f"target must be a contiguous {target.dtype} tensor of shape {shape} on {feat.device}")
+        n = p
+        if pages is not None:
+            if (pages.dtype != torch.int32 or pages.dim() != 1 or pages.numel() < 1 or not pages.is_contiguous()
+                    or pages.device != feat.device):
+                raise ValueError(f"pages must be a non-empty contiguous int32 [N] tensor on {feat.device}")
+            n = pages.numel()
+        thr = None
+        if thresholds is not None:
+            if len(thresholds) < c:
+                raise ValueError(f"thresholds needs {c} values")
+            thr = (ctypes.c_float * c)(*[float(t) for t in list(thresholds)[:c]])
+        probs, k, hist = None, 0, None
+        if sweep is not None:
+            k = len(sweep)
+            if not 1 <= k <= SCORE_MAX_K:
+                raise ValueError(f"sweep needs 1..{SCORE_MAX_K} probabilities, got {k}")
+            probs = (ctypes.c_float * k)(*[float(q) for q in sweep])
+            hist = torch.empty((n, c, 2, k + 1), device=feat.device, dtype=torch.int64)
+        size = ctypes.sizeof(ScoreEntry)
+        if entries is None:
+            entries = torch.empty((n, c, size), device=feat.device, dtype=torch.uint8)
+        elif (entries.dtype != torch.uint8 or tuple(entries.shape) != (n, c, size) or not entries.is_contiguous()
+              or entries.device != feat.device or entries.data_ptr() % 8):
+            raise ValueError(f"entries must be a contiguous uint8 tensor of shape {(n, c, size)} on {feat.device}")
+        with self.lock:
+            check(self.lib.unet_head_score(self._h, feat.data_ptr(), HEAD_FEAT_DTYPES[feat.dtype], weight.data_ptr(),
+                                           bias.data_ptr(), target.data_ptr(), kind, _ptr(pages), p, n, c, h, w, thr,
+                                           entries.data_ptr(), probs, k, _ptr(hist), stream), "unet_head_score")
+        return entries, hist
 
     def forward_timed(self, x: torch.Tensor, logits: torch.Tensor | None, masks: torch.Tensor | None,
                       mask_kind: int, stream: int, layout: int = LAYOUT_NCHW) -> list:
