@@ -42,7 +42,7 @@ extern "C" {
                                     unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
                                     unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed;
                                     then unet_head_step_reserve, unet_head_step, unet_adamw_config;
-                                    then unet_head_score_reserve, unet_head_score) */
+                                    then unet_head_score_reserve, unet_head_score; then unet_launch_split_at) */
 
 /* error codes */
 #define UNET_OK 0
@@ -193,6 +193,13 @@ const char* unet_launch_label(const unet_handle* h, int i);
  * whose under-filled layers may run finer row tiles; N = 0 (or N above the limit) gives the
  * large-batch labels of unet_launch_label.  The string lives until the calling thread's next call. */
 const char* unet_launch_label_at(const unet_handle* h, int i, int N, int H, int W);
+
+/* The small-batch plan's choice for launch i of a forward of N x H x W, which the label does not spell out:
+ * *ks = K slices (1: the launch runs unsplit), *rows = row tile of the launch (0: the layer's own, else 64 or
+ * 128: finer tiles over the layer's packing).  (1, 0) for a slot that launches nothing, for N = 0 and for N
+ * above unet_small_batch_limit.  Host arithmetic only: no HIP call, no allocation.  UNET_EINVAL for a bad
+ * index, a negative shape or null pointers. */
+int unet_launch_split_at(const unet_handle* h, int i, int N, int H, int W, int* ks, int* rows);
 
 /* Largest batch of the small-batch (split-K) plan, 0 when it is off (UNET_MI355X_KSPLIT=0 at
  * unet_create).  An image's outputs are bitwise the same for every N <= the limit, and for every N

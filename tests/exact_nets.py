@@ -374,6 +374,20 @@ def routing_reference(seed: int, c_in: int, n: int, h: int, w: int, bits: int = 
     return x, ref
 
 
+def oracle_stored(sd, x: np.ndarray) -> "OrderedDict[str, np.ndarray]":
+    """The fp32 oracle's logits and every tensor a forward stores but c8a, by ``UNet.intermediate`` name, for ANY
+    weights (conv1.0's BatchNorm is not the identity there, so c8a is left to the routing networks): what a
+    tolerance test of real-valued weights compares the stored intermediates with."""
+    sdt = {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}
+    logits, it = orc.unet_forward(sdt, torch.from_numpy(np.array(x)), return_intermediates=True)
+    with torch.no_grad():
+        ups = {"u4": orc.up(sdt, "up4", it["bn"]), "u3": orc.up(sdt, "up3", it["c5"]),
+               "u2": orc.up(sdt, "up2", it["c6"]), "u1": orc.up(sdt, "up1", it["c7"])}
+    ref = OrderedDict((k, (ups[k] if k in ups else it[k]).numpy()) for k in FORWARD_ORDER[:-1] if k != "c8a")
+    ref["logits"] = logits.numpy()
+    return ref
+
+
 # (seed, c_in, n, h, w) of the routing tests: the minimum size (1-pixel bottleneck; N = 1 takes the small-batch
 # split-K plan, N = 6 the large-batch plan with partial tiles at every level), a ragged size on three seeds, the
 # size forced kernel configurations run at, and full-size pages (persistent walkers and rings wrap)

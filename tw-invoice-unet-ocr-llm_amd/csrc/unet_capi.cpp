@@ -1853,6 +1853,20 @@ const char* unet_launch_label_at(const unet_handle* h, int i, int N, int H, int 
   return labels[i].c_str();
 }
 
+int unet_launch_split_at(const unet_handle* h, int i, int N, int H, int W, int* ks, int* rows) {
+  if (!h || !ks || !rows) return fail(UNET_EINVAL, "null argument");
+  if (i < 0 || i >= UNET_NUM_LAUNCHES || N < 0 || H < 0 || W < 0) return fail(UNET_EINVAL, "bad launch index or shape");
+  *ks = 1;
+  *rows = 0;
+  if (i == 0) return UNET_OK;   // the first conv / the input pre-cast: never split
+  const Step st = resolve(h, kLaunches[i - 1], N);
+  if (!st.L) return UNET_OK;    // a fused up1 launches nothing
+  const Split sp = step_split(h, st, N, H, W);
+  *ks = sp.ks;
+  *rows = sp.rows;
+  return UNET_OK;
+}
+
 int unet_small_batch_limit(const unet_handle* h) {
   if (!h) return fail(UNET_EINVAL, "null handle");
   return h->ksplit_max > 1 ? kSmallBatch : 0;

@@ -125,6 +125,7 @@ SIGNATURES = {
     "unet_num_launches": (_i, []),
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
+    "unet_launch_split_at": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "unet_small_batch_limit": (_i, [_vp]),
     "unet_photo_graph_create": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, ctypes.c_double, _vp, _vp,
                                      _vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
@@ -621,6 +622,17 @@ class Handle:
     def launch_labels_at(self, n: int, h: int, w: int) -> list:
         """launch_labels for a forward of n x h x w (the small-batch plan's kernels at n <= its limit)."""
         return [self.lib.unet_launch_label_at(self._h, i, n, h, w).decode() for i in range(self.lib.unet_num_launches())]
+
+    def launch_split_at(self, n: int, h: int, w: int) -> list:
+        """(ks, rows) of every launch slot for a forward of n x h x w (unet_launch_split_at: K slices, 1 = unsplit;
+        row tile, 0 = the layer's own).  Host arithmetic only."""
+        out = []
+        ks, rows = _i(), _i()
+        for i in range(self.lib.unet_num_launches()):
+            check(self.lib.unet_launch_split_at(self._h, i, n, h, w, ctypes.byref(ks), ctypes.byref(rows)),
+                  "unet_launch_split_at")
+            out.append((ks.value, rows.value))
+        return out
 
     # ---- multi-GPU extras (include/unet_mi355x.h): RCCL all-gather for a host without torch.distributed
     @staticmethod
