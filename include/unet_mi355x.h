@@ -42,7 +42,8 @@ extern "C" {
                                     unet_head_reserve, unet_head_forward, unet_head_backward; then unet_debug_fill,
                                     unet_block_debug_fill; then unet_head_forward_typed, unet_head_backward_typed;
                                     then unet_head_step_reserve, unet_head_step, unet_adamw_config;
-                                    then unet_head_score_reserve, unet_head_score; then unet_launch_split_at) */
+                                    then unet_head_score_reserve, unet_head_score; then unet_launch_split_at;
+                                    then unet_launch_walk_at, unet_block_launch_walk_at) */
 
 /* error codes */
 #define UNET_OK 0
@@ -200,6 +201,16 @@ const char* unet_launch_label_at(const unet_handle* h, int i, int N, int H, int 
  * above unet_small_batch_limit.  Host arithmetic only: no HIP call, no allocation.  UNET_EINVAL for a bad
  * index, a negative shape or null pointers. */
 int unet_launch_split_at(const unet_handle* h, int i, int N, int H, int W, int* ks, int* rows);
+
+/* The walk of launch i of a forward of N x H x W.  The ring kernels are persistent: every row tile of the launch
+ * has *slots walkers, and walker s takes the pixel tiles s, s + *slots, ... (for a split launch a tile means a
+ * (tile, K slice) pair, and a walker keeps one slice); *items = the most tiles one walker takes.  (0, 0) for a
+ * launch that is no ring kernel (the first conv, the pre-cast, the fp32 LDS-halo family), for a slot that
+ * launches nothing and for N = 0.  The environment variable UNET_MI355X_WALKERS=k, read by unet_create and
+ * unet_block_create (A/B and tests only; unset or 0 = no cap), caps *slots at k (k rounded down to a multiple of
+ * the slice count, never below it).  The launcher's own arithmetic, with no launch, no HIP call and no
+ * allocation.  UNET_EINVAL for a bad index, a negative shape or null pointers. */
+int unet_launch_walk_at(const unet_handle* h, int i, int N, int H, int W, int* slots, int* items);
 
 /* Largest batch of the small-batch (split-K) plan, 0 when it is off (UNET_MI355X_KSPLIT=0 at
  * unet_create).  An image's outputs are bitwise the same for every N <= the limit, and for every N
@@ -505,6 +516,8 @@ int unet_block_reserve(unet_block* b, int N, int H, int W);
 int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, int W, void* hip_stream);
 /* unet_debug_fill for a block: its workspace (unet_block_reserve), under the same rules. */
 int unet_block_debug_fill(unet_block* b, int byte, void* hip_stream);
+/* unet_launch_walk_at for a block's conv i (0 = net.0, 1 = net.3) at N x H x W. */
+int unet_block_launch_walk_at(const unet_block* b, int i, int N, int H, int W, int* slots, int* items);
 int unet_block_destroy(unet_block* b);
 
 /* Message of the last error on this thread ("" if none). */

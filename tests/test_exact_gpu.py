@@ -146,11 +146,13 @@ def _unet(dtype):
     return UNet(3, 3, compute_dtype=dtype).to(DEV).eval()
 
 
-def _run_block(blk: en.ExactBlock, dtype):
+def _run_block(blk: en.ExactBlock, dtype, pre=None):
     dc = getattr(_unet(dtype), blk.name)
     dc.close()                                   # a fresh native block (it reads its environment when created)
     dc.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in blk.sd.items()})
     try:
+        if pre is not None:                      # (the DoubleConv, before its forward)
+            pre(dc)
         with torch.no_grad():
             got = dc(torch.from_numpy(np.array(blk.x)).to(DEV)).cpu().numpy()
     finally:
@@ -158,8 +160,8 @@ def _run_block(blk: en.ExactBlock, dtype):
     return got
 
 
-def _check_block(blk, dtype, what):
-    got, want = _run_block(blk, dtype), blk.expected(dtype)
+def _check_block(blk, dtype, what, pre=None):
+    got, want = _run_block(blk, dtype, pre), blk.expected(dtype)
     assert got.shape == want.shape
     if not np.array_equal(got, want):
         pytest.fail(f"{dtype} {what}: " + en.describe_mismatch(

@@ -38,15 +38,17 @@ def _reference_masks(ref, n):
                      for i in range(n)])
 
 
-def _check(case, plan, tag="", r12=None):
+def _check(case, plan, tag="", r12=None, pre=None):
     """One model, one input: logits and every stored intermediate, masks (u8 and packed) and boxes, all bitwise
-    against the rounding reference (tests/test_exact_gpu.py _check_routing on the rounding operands).  Returns
-    the launch labels of the forward."""
+    against the rounding reference (tests/test_exact_gpu.py _check_routing on the rounding operands).  ``pre``
+    (optional) is called with the model before its first forward.  Returns the launch labels of the forward."""
     seed, c_in, n, h, w = case
     x, ref = en.rounding_reference(*case, plan, r12=r12)
     sd = en.rounding_state_dict(seed, c_in) if r12 is None else en.routing_state_dict_r12(seed, c_in, r12)
     m = _model(sd, c_in, plan)
     try:
+        if pre is not None:
+            pre(m)
         xd = torch.from_numpy(np.array(x)).to(DEV)
         with torch.no_grad():
             logits = m(xd)

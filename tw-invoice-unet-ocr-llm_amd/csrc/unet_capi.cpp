@@ -156,6 +156,9 @@ struct unet_handle {
   int f32x3 = 0;   // fp32 plan: operands as three bf16 terms on the bf16 MFMA pipe (IgemmArgs::x3): 2 = split-once
                    // 128-row tiles on the Cout >= 128 layers, 1 = 64-row tiles everywhere
   int ksplit_force[21] = {};
+  // cap on the walkers per row tile of every persistent ring launch (UNET_MI355X_WALKERS; 0 = none: A/B runs and
+  // the tests of walkers that take several tiles each; walk_of, unet_launch_walk_at)
+  int walkers = 0;
   void* part = nullptr;   // the current forward's partial buffer (workspace region Buffers::part)
   // mask-box sync entries (launch_mask_boxes: kSyncInts ints per (image, field), idle between
   // launches), grown by unet_reserve
@@ -1066,6 +1069,12 @@ void build_labels_at(const unet_handle* h, int N, int H, int W, std::string (&ou
 }
 void build_labels(unet_handle* h) { build_labels_at(h, 0, 0, 0, h->labels); }
 
+// UNET_MI355X_WALKERS=k: at most k walkers per row tile of a persistent ring launch (unset, 0 or negative: no cap)
+int env_walkers() {
+  const char* v = std::getenv("UNET_MI355X_WALKERS");
+  return v ? std::max(0, std::atoi(v)) : 0;
+}
+
 // The "i:v,..." lists of the A/B override variables: each(i, v, item) for every item with a colon; the caller
 // decides what it accepts.
 template <typename F>
@@ -1259,6 +1268,7 @@ int unet_create(const unet_config* cfg, unet_handle** out) {
   parse_pairs(std::getenv("UNET_MI355X_KSPLIT_FORCE"), [&](int li, int ks, const std::string&) {   // "i:ks,..." (A/B runs)
     if (li >= 0 && li < 21) h->ksplit_force[li] = ks;
   });
+  h->walkers = env_walkers();
   build_labels(h);   // after every layer's configuration (3x3 and ConvTranspose) is final
   DeviceGuard g(cfg->device);
   rc = init_handle(h);
@@ -1394,11 +1404,14 @@ int unet_reserve(unet_handle* h, int N, int H, int W) {
 namespace {
 
 // id: layer_split's (Step::r.id; < 0 = never split: the fused first conv, the stand-alone block)
-int run_igemm(unet_handle* h, int id, const Layer& L, int epi, const void* in, int N, int H, int W, int ldi,
+// probe (unet_launch_walk_at): the launcher reports the launch's walk and launches nothing; a ring launch only
+int run_igemm(const unet_handle* h, int id, const Layer& L, int epi, const void* in, int N, int H, int W, int ldi,
               void* out, int ldo, int out_off, void* out2, int ldo2, hipStream_t s,
               float* logits = nullptr, void* masks = nullptr, int mask_kind = MASK_NONE,
-              const void* x0 = nullptr) {
-  IgemmArgs a{};
+              const void* x0 = nullptr, Walk* probe = nullptr) {
+  IgemmLaunch a{};
+  a.walkers = h->walkers;
+  a.probe = probe;
   a.in = in;
   a.wgt = L.w;
   a.bias = L.b;
@@ -1445,7 +1458,7 @@ int run_igemm(unet_handle* h, int id, const Layer& L, int epi, const void* in, i
       a.n_ct = L.ctot / sp.rows;
     }
     hipError_t e = launch_igemm(L.dt, L.dt, L.dt, L.cfg, L.taps, EPI_PARTIAL, a, s);
-    if (e == hipSuccess) e = launch_splitk_reduce(L.dto, epi == EPI_POOL ? L.dtq : L.dto, epi, a, s);
+    if (e == hipSuccess && !probe) e = launch_splitk_reduce(L.dto, epi == EPI_POOL ? L.dtq : L.dto, epi, a, s);
     return hip_ok(e, "split-K igemm launch");
   }
   return hip_ok(launch_igemm(L.dt, L.dto, epi == EPI_POOL ? L.dtq : L.dto, cfg, L.taps, epi, a, s), "igemm launch");
@@ -1867,6 +1880,32 @@ int unet_launch_split_at(const unet_handle* h, int i, int N, int H, int W, int* 
   return UNET_OK;
 }
 
+namespace {
+// The walk of one igemm launch as run_igemm would launch it (no launch: the launcher's own arithmetic through
+// IgemmLaunch::probe); {0, 0} for a launch that is no persistent ring kernel or has nothing to do.
+int walk_at(const unet_handle* h, int id, const Layer& L, int epi, int N, int H, int W, Walk* wk) {
+  *wk = Walk{0, 0};
+  if (N <= 0 || H <= 0 || W <= 0 || !(cfg_is_ring(L.cfg) || cfg_is_tring(L.cfg))) return UNET_OK;
+  return run_igemm(h, id, L, epi, nullptr, N, H, W, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, MASK_NONE,
+                   nullptr, wk);
+}
+}  // namespace
+
+int unet_launch_walk_at(const unet_handle* h, int i, int N, int H, int W, int* slots, int* items) {
+  if (!h || !slots || !items) return fail(UNET_EINVAL, "null argument");
+  if (i < 0 || i >= UNET_NUM_LAUNCHES || N < 0 || H < 0 || W < 0) return fail(UNET_EINVAL, "bad launch index or shape");
+  *slots = *items = 0;
+  if (i == 0) return UNET_OK;   // the first conv / the input pre-cast: one block per tile, no walk
+  const Step st = resolve(h, kLaunches[i - 1], N);
+  if (!st.L) return UNET_OK;    // a fused up1 launches nothing
+  Walk wk;
+  const int rc = walk_at(h, st.r.id, *st.L, st.r.epi, N, H >> st.r.level, W >> st.r.level, &wk);
+  if (rc) return rc;
+  *slots = wk.slots;
+  *items = wk.items;
+  return UNET_OK;
+}
+
 int unet_small_batch_limit(const unet_handle* h) {
   if (!h) return fail(UNET_EINVAL, "null handle");
   return h->ksplit_max > 1 ? kSmallBatch : 0;
@@ -2212,6 +2251,7 @@ int unet_block_create(const unet_block_config* cfg, unet_block** out) {
   h.cfg.dtype = cfg->dtype;
   h.cfg.device = cfg->device;
   h.ksplit_max = 0;
+  h.walkers = env_walkers();
   h.f32x3 = f32x3_plan(cfg->dtype) != 0;
   // the mixed plan's storage type at this block's resolution level in the reference network: fp16 up to
   // 128 channels (levels 0-1), bf16 beyond (levels 2-4)
@@ -2304,6 +2344,19 @@ int unet_block_forward(unet_block* b, const float* x, float* y, int N, int H, in
   if (rc) return rc;
   HIP_CHECK(launch_nhwc_to_nchw(t, outb, N, b->cout, H, W, y, s), "block output transpose");
   mark_done(&h, s);
+  return UNET_OK;
+}
+
+int unet_block_launch_walk_at(const unet_block* b, int i, int N, int H, int W, int* slots, int* items) {
+  if (!b || !slots || !items) return fail(UNET_EINVAL, "null argument");
+  if (i < 0 || i > 1 || N < 0 || H < 0 || W < 0) return fail(UNET_EINVAL, "bad conv index or shape");
+  *slots = *items = 0;
+  if (i == 0 && b->first) return UNET_OK;   // the first-conv kernel: one block per tile, no walk
+  Walk wk;
+  const int rc = walk_at(&b->core, -1, b->core.L[i], EPI_STORE, N, H, W, &wk);
+  if (rc) return rc;
+  *slots = wk.slots;
+  *items = wk.items;
   return UNET_OK;
 }
 

@@ -72,6 +72,36 @@ struct IgemmArgs {
                 // from a register-prefetched halo (conv3x3_x3w_kernel, CFG_HALO_X3W: the 64-channel layers)
 };
 
+// The walk of a persistent ring launch (conv3x3_ring_kernel, conv3x3_ring8_kernel, convT_ring_kernel): `slots`
+// walkers per row tile, walker s taking the items s, s + slots, ... (pixel tiles; (tile, K slice) pairs of an
+// EPI_PARTIAL launch), `items` = the most one walker takes.
+struct Walk {
+  int slots, items;
+};
+// The one place that sizes a walk (launch_ring8, launch_ring, launch_tring and through them unet_launch_walk_at).
+// resident: blocks the chip holds at once (kNumCUs x blocks per CU); n_mt: items of the launch, a multiple of ks;
+// ks: K slices of an EPI_PARTIAL launch (1 otherwise) -- the walker count stays a multiple of it, so a walker keeps
+// ONE slice; cap: UNET_MI355X_WALKERS (0 = none), at most that many walkers, never fewer than ks.
+inline Walk walk_of(int resident, int n_ct, int n_mt, int ks, int cap) {
+  int n = resident / n_ct;
+  n -= n % ks;
+  if (n < ks) n = ks;
+  if (n > n_mt) n = n_mt;
+  if (cap > 0) {
+    const int k = cap - cap % ks < ks ? ks : cap - cap % ks;
+    if (n > k) n = k;
+  }
+  return Walk{n, n > 0 ? (n_mt + n - 1) / n : 0};
+}
+
+// A launch as the host passes it to launch_igemm: the kernel arguments (the kernels take the IgemmArgs base by
+// value and never see the rest) and what only the launcher reads.
+struct IgemmLaunch : IgemmArgs {
+  int walkers = 0;         // cap on the walkers per row tile of a persistent ring launch (walk_of's cap)
+  Walk* probe = nullptr;   // set: a ring launcher reports its walk here and launches nothing; the data pointers
+                           // may then be null.  Every other launcher refuses (hipErrorInvalidValue).
+};
+
 struct FirstConvArgs {
   const float* x;      // NCHW fp32 input [N][C][H][W]
   const float* w;      // [64][C][3][3] folded (fp32 VALU path)
@@ -131,7 +161,7 @@ int cfg_limit();            // valid Cfg values of this build (ablation builds: 
 
 // t: operand (activation + weight) type; to / tq: types of the output / pooled map (t unless
 // the layer sits at a seam of the mixed bf16/fp16 plan)
-hipError_t launch_igemm(DType t, DType to, DType tq, int cfg, int taps, int epi, const IgemmArgs& a,
+hipError_t launch_igemm(DType t, DType to, DType tq, int cfg, int taps, int epi, const IgemmLaunch& a,
                         hipStream_t s);
 hipError_t launch_first_conv(DType t, const FirstConvArgs& a, hipStream_t s);
 // Split-K reduction of an EPI_PARTIAL launch: out = epilogue(bias + part[0] + part[1] + ...) in

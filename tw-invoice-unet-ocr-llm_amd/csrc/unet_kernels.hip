@@ -2720,25 +2720,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ring8_kernel(const IgemmArgs a
 }
 
 template <typename T, int TCW, int NS, int EPI, int TPS, int WST, typename TO, typename TQ, int HS = 0, int ABL = 0>
-static hipError_t launch_ring8(const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_ring8(const IgemmLaunch& a, hipStream_t s) {
   using G = Ring8Geom<T, TCW, NS, TPS, WST, HS>;
   if constexpr (HS != 0) {
-    if (a.Cin != 2 * G::BKE || a.c0 < 1 || a.c0 > 3 || !a.x0 || !a.w0p || !a.b0) return hipErrorInvalidValue;
+    if (a.Cin != 2 * G::BKE || a.c0 < 1 || a.c0 > 3 || (!a.probe && (!a.x0 || !a.w0p || !a.b0))) return hipErrorInvalidValue;
   }
   if (a.tiles_y != (a.H + 15) / 16 || a.tiles_x != (a.W + G::TW - 1) / G::TW) return hipErrorInvalidValue;
   if (a.Cin % G::BKE || a.Ctot % G::BR || a.n_ct != a.Ctot / G::BR) return hipErrorInvalidValue;
   if (WST && (9 / TPS) * (a.Cin / G::BKE) > G::WST_STEPS) return hipErrorInvalidValue;
   const int KS = EPI == EPI_PARTIAL ? a.ksplit : 1;
-  if (KS < 1 || a.Cin % (G::BKE * KS) || (EPI == EPI_PARTIAL && !a.part)) return hipErrorInvalidValue;
+  if (KS < 1 || a.Cin % (G::BKE * KS) || (EPI == EPI_PARTIAL && !a.part && !a.probe)) return hipErrorInvalidValue;
   constexpr bool fine = TCW == 4 && NS == 3 && TPS == 3 && WST == 0 && HS == 0 && EPI != EPI_UPFUSE;
   if (a.src_br && (!(EPI == EPI_PARTIAL || fine) || a.src_br % G::BR || a.Ctot % a.src_br)) return hipErrorInvalidValue;
   const int n_mt = a.N * a.tiles_y * a.tiles_x * KS;   // items: (pixel tile, K slice)
-  int n_slots = kNumCUs / a.n_ct;   // one 512-thread block per CU
-  n_slots -= n_slots % KS;          // every walker keeps one K slice (n_mt is a multiple of KS)
-  if (n_slots < KS) n_slots = KS;
-  if (n_slots > n_mt) n_slots = n_mt;
-  hipLaunchKernelGGL((conv3x3_ring8_kernel<T, TCW, NS, EPI, TPS, WST, TO, TQ, HS, ABL>), dim3(a.n_ct * n_slots), dim3(512),
-                     0, s, a);
+  // one 512-thread block per CU; every walker keeps one K slice (n_mt is a multiple of KS)
+  const Walk wk = walk_of(kNumCUs, a.n_ct, n_mt, KS, a.walkers);
+  if (a.probe) { *a.probe = wk; return hipSuccess; }
+  hipLaunchKernelGGL((conv3x3_ring8_kernel<T, TCW, NS, EPI, TPS, WST, TO, TQ, HS, ABL>), dim3(a.n_ct * wk.slots), dim3(512),
+                     0, s, static_cast<const IgemmArgs&>(a));
   return hipGetLastError();
 }
 
@@ -3126,10 +3125,10 @@ static hipError_t launch_x3w(const IgemmArgs& a, hipStream_t s) {
 
 template <typename T, int WR, int WPX, int TCW, int NS, int EPI, int TPS, int HS, typename TO, typename TQ, int ABL = 0,
           int TH = 16, int TW = 16>
-static hipError_t launch_ring(const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_ring(const IgemmLaunch& a, hipStream_t s) {
   using G = RingGeom<T, WR, WPX, TCW, NS, TPS, HS, TH, TW>;
   if constexpr (HS != 0) {
-    if (a.Cin != 2 * G::BKE || a.c0 < 1 || a.c0 > 3 || !a.x0 || !a.w0p || !a.b0) return hipErrorInvalidValue;
+    if (a.Cin != 2 * G::BKE || a.c0 < 1 || a.c0 > 3 || (!a.probe && (!a.x0 || !a.w0p || !a.b0))) return hipErrorInvalidValue;
   }
   if (a.tiles_y != (a.H + TH - 1) / TH || a.tiles_x != (a.W + TW - 1) / TW) return hipErrorInvalidValue;
   if ((TH != 16 || TW != 16 || EPI == EPI_UPFUSE) && (long long)a.H * a.W * a.ldi * (long long)sizeof(T) >= (1LL << 31))
@@ -3137,45 +3136,44 @@ static hipError_t launch_ring(const IgemmArgs& a, hipStream_t s) {
   if (a.Cin % G::BKE || a.Ctot % G::BR || a.n_ct != a.Ctot / G::BR) return hipErrorInvalidValue;
   const int n_mt = a.N * a.tiles_y * a.tiles_x;
   constexpr int per_cu = G::NW >= 8 ? 1 : G::BLOCKS_PER_CU;   // 8-wave blocks: registers allow one per CU
-  int n_slots = (kNumCUs * per_cu) / a.n_ct;
-  if (n_slots < 1) n_slots = 1;
-  if (n_slots > n_mt) n_slots = n_mt;
+  const Walk wk = walk_of(kNumCUs * per_cu, a.n_ct, n_mt, 1, a.walkers);
+  if (a.probe) { *a.probe = wk; return hipSuccess; }
 #ifdef UNET_ABLATION
   if constexpr (ABL != 0) {
-    hipLaunchKernelGGL((conv3x3_ring_abl_kernel<T, WR, WPX, TCW, NS, EPI, TPS, HS, TO, TQ, ABL>), dim3(a.n_ct * n_slots),
-                       dim3(64 * WR * WPX), 0, s, a);
+    hipLaunchKernelGGL((conv3x3_ring_abl_kernel<T, WR, WPX, TCW, NS, EPI, TPS, HS, TO, TQ, ABL>), dim3(a.n_ct * wk.slots),
+                       dim3(64 * WR * WPX), 0, s, static_cast<const IgemmArgs&>(a));
     return hipGetLastError();
   }
 #endif
-  hipLaunchKernelGGL((conv3x3_ring_kernel<T, WR, WPX, TCW, NS, EPI, TPS, HS, TO, TQ, TH, TW>), dim3(a.n_ct * n_slots),
-                     dim3(64 * WR * WPX), 0, s, a);
+  hipLaunchKernelGGL((conv3x3_ring_kernel<T, WR, WPX, TCW, NS, EPI, TPS, HS, TO, TQ, TH, TW>), dim3(a.n_ct * wk.slots),
+                     dim3(64 * WR * WPX), 0, s, static_cast<const IgemmArgs&>(a));
   return hipGetLastError();
 }
 
 template <typename T, int TCW, int NS, int WRW, typename TO>
-static hipError_t launch_tring(const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_tring(const IgemmLaunch& a, hipStream_t s) {
   constexpr int BR = 16 * TCW * WRW, LDS = NS * (BR * 64 + 256 * 64);
   if (a.tiles_y != (a.H + 15) / 16 || a.tiles_x != (a.W + 15) / 16) return hipErrorInvalidValue;
   if (a.src_br && (WRW != 1 || a.src_br % BR || a.Ctot % a.src_br)) return hipErrorInvalidValue;
   if (a.Cin % (64 / (int)sizeof(T)) || a.Ctot % BR || a.n_ct != a.Ctot / BR) return hipErrorInvalidValue;
   const int n_mt = a.N * a.tiles_y * a.tiles_x;
-  int n_slots = (kNumCUs * ((160 * 1024) / LDS)) / a.n_ct;
-  if (n_slots < 1) n_slots = 1;
-  if (n_slots > n_mt) n_slots = n_mt;
-  hipLaunchKernelGGL((convT_ring_kernel<T, TCW, NS, WRW, TO>), dim3(a.n_ct * n_slots), dim3(256 * WRW), 0, s, a);
+  const Walk wk = walk_of(kNumCUs * ((160 * 1024) / LDS), a.n_ct, n_mt, 1, a.walkers);
+  if (a.probe) { *a.probe = wk; return hipSuccess; }
+  hipLaunchKernelGGL((convT_ring_kernel<T, TCW, NS, WRW, TO>), dim3(a.n_ct * wk.slots), dim3(256 * WRW), 0, s,
+                     static_cast<const IgemmArgs&>(a));
   return hipGetLastError();
 }
 
 // 3x3 layers.  T = operand type, TO / TQ = output / pooled-map types (the LDS-halo family runs
 // only with TO = TQ = T: it is the fp32 path).
 template <typename T, typename TO, typename TQ, int EPI, int ABL = 0>
-static hipError_t launch_3x3(int cfg, const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_3x3(int cfg, const IgemmLaunch& a, hipStream_t s) {
   constexpr bool same = std::is_same<T, TO>::value && std::is_same<TO, TQ>::value;
   if constexpr (EPI == EPI_UPFUSE) {   // conv2.3 + up1: the 16-bit 128-row ring only (one row tile)
     if constexpr (sizeof(T) == 2 && ABL == 0) {
-      if (cfg == CFG_RING_R128 && a.n_ct == 1 && a.Cout == 128 && a.out2 && a.bias2)
+      if (cfg == CFG_RING_R128 && a.n_ct == 1 && a.Cout == 128 && (a.probe || (a.out2 && a.bias2)))
         return launch_ring<T, 1, 4, 8, 3, EPI_UPFUSE, 1, 0, TO, TQ>(a, s);
-      if (cfg == CFG_RING8_R128 && a.n_ct == 1 && a.Cout == 128 && a.out2 && a.bias2)
+      if (cfg == CFG_RING8_R128 && a.n_ct == 1 && a.Cout == 128 && (a.probe || (a.out2 && a.bias2)))
         return launch_ring8<T, 8, 3, EPI_UPFUSE, 3, 0, TO, TQ>(a, s);
     }
     return hipErrorInvalidValue;
@@ -3261,7 +3259,7 @@ static hipError_t launch_3x3(int cfg, const IgemmArgs& a, hipStream_t s) {
 
 // ConvTranspose2d(k2, s2) layers (1-tap GEMM + pixel-shuffle scatter).  TO = output type.
 template <typename T, typename TO, int EPI = EPI_UPSCATTER>
-static hipError_t launch_up(int cfg, const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_up(int cfg, const IgemmLaunch& a, hipStream_t s) {
   if constexpr (EPI == EPI_PARTIAL) {   // split-K slices of the LDS-halo ConvTranspose (the fp32 path)
     if (cfg == CFG_HALO_R128) return launch_halo<T, 1, 4, 8, 2, EPI_PARTIAL, 1>(a, s);
     if constexpr (sizeof(T) == 4)
@@ -3284,7 +3282,7 @@ static hipError_t launch_up(int cfg, const IgemmArgs& a, hipStream_t s) {
 }
 
 template <typename T, typename TO, typename TQ>
-static hipError_t launch_typed(int cfg, int taps, int epi, const IgemmArgs& a, hipStream_t s) {
+static hipError_t launch_typed(int cfg, int taps, int epi, const IgemmLaunch& a, hipStream_t s) {
 #ifdef UNET_ABLATION
   if (taps == 9 && cfg >= CFG_COUNT) {   // cfg = base + 16 * ablation (csrc/unet_kernels.hip ring_body)
     const int base = cfg % 16;
@@ -3324,7 +3322,8 @@ static hipError_t launch_typed(int cfg, int taps, int epi, const IgemmArgs& a, h
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_igemm(DType t, DType to, DType tq, int cfg, int taps, int epi, const IgemmArgs& a, hipStream_t s) {
+hipError_t launch_igemm(DType t, DType to, DType tq, int cfg, int taps, int epi, const IgemmLaunch& a, hipStream_t s) {
+  if (a.probe && !(cfg_is_ring(cfg) || cfg_is_tring(cfg))) return hipErrorInvalidValue;   // only the rings walk
   if (t == to && to == tq) {
     switch (t) {
       case DType::F32: return launch_typed<float, float, float>(cfg, taps, epi, a, s);

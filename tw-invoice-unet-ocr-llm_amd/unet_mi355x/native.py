@@ -126,6 +126,7 @@ SIGNATURES = {
     "unet_launch_label": (ctypes.c_char_p, [_vp, _i]),
     "unet_launch_label_at": (ctypes.c_char_p, [_vp, _i, _i, _i, _i]),
     "unet_launch_split_at": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "unet_launch_walk_at": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "unet_small_batch_limit": (_i, [_vp]),
     "unet_photo_graph_create": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, ctypes.c_double, _vp, _vp,
                                      _vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
@@ -146,6 +147,7 @@ SIGNATURES = {
     "unet_block_reserve": (_i, [_vp, _i, _i, _i]),
     "unet_block_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "unet_block_debug_fill": (_i, [_vp, _i, _vp]),
+    "unet_block_launch_walk_at": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "unet_block_destroy": (_i, [_vp]),
     "unet_last_error": (ctypes.c_char_p, []),
     "unet_abi_version": (_i, []),
@@ -634,6 +636,18 @@ class Handle:
             out.append((ks.value, rows.value))
         return out
 
+    def launch_walk_at(self, n: int, h: int, w: int) -> list:
+        """(slots, items) of every launch slot for a forward of n x h x w (unet_launch_walk_at: walkers per row tile
+        of a persistent ring launch and the most tiles one of them takes; (0, 0) for every other launch).  Host
+        arithmetic only."""
+        out = []
+        slots, items = _i(), _i()
+        for i in range(self.lib.unet_num_launches()):
+            check(self.lib.unet_launch_walk_at(self._h, i, n, h, w, ctypes.byref(slots), ctypes.byref(items)),
+                  "unet_launch_walk_at")
+            out.append((slots.value, items.value))
+        return out
+
     # ---- multi-GPU extras (include/unet_mi355x.h): RCCL all-gather for a host without torch.distributed
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -740,6 +754,16 @@ class Block:
         """unet_block_debug_fill: the block's workspace set to ``byte``, stream-ordered."""
         with self.lock:
             check(self.lib.unet_block_debug_fill(self._b, int(byte), stream), "unet_block_debug_fill")
+
+    def launch_walk_at(self, n: int, h: int, w: int) -> list:
+        """(slots, items) of the block's two convs at n x h x w (unet_block_launch_walk_at)."""
+        out = []
+        slots, items = _i(), _i()
+        for i in range(2):
+            check(self.lib.unet_block_launch_walk_at(self._b, i, n, h, w, ctypes.byref(slots), ctypes.byref(items)),
+                  "unet_block_launch_walk_at")
+            out.append((slots.value, items.value))
+        return out
 
     def close(self) -> None:
         if getattr(self, "_b", None):
